@@ -27,7 +27,17 @@ GPU); value = N x 8 GiB x K / the slowest rank's time.  No collective touches
 the data: torch.distributed carries only the barriers, the max-time reduction
 and the check flags.
 
-End to end (key `e2e`, on by default, --e2e-steps 0 turns it off): after the
+A plain run (`--gpus 1 --steps K --warmup W`) does only what `value` needs:
+it fills the arenas, fills the pipeline, warms up, times the K steps of the
+random workload and prints the line; --dump-outputs DIR also writes the last
+timed step's results (dump_outputs).  Everything else is behind --full: the
+Zipf line (key `zipf`), the oracle checks (`check_vs_oracle`), the
+single-batch latency (`single_batch`), the probed lifetime leg (`lifetime`),
+the e2e leg (`e2e`) and the CPU baseline (`cpu_baseline`); the switches that
+trim them (--workload, --no-check, --no-lifetime, --e2e-steps,
+--no-cpu-baseline) act under --full.
+
+End to end (key `e2e`, with --full, --e2e-steps 0 turns it off): after the
 device-resident lines, the same pipeline with every step's batch copied from
 pinned host memory (hbx_alloc_pinned + hbx_memcpy_h2d_async on the scan
 stream, overlapped with the previous batches' kernels), results back in host
@@ -101,7 +111,7 @@ def parse():
                     help="strong (default, configs[2]): each step's files are split across the ranks; "
                          "weak: every rank takes a whole batch of its own files per step (per-GPU work fixed)")
     ap.add_argument("--workload", choices=["both", "random", "zipf"], default="both",
-                    help="both: the random headline plus a Zipf-duplicate line under key 'zipf'")
+                    help="both: the random headline plus, with --full, a Zipf-duplicate line under key 'zipf'")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this process may use")
     ap.add_argument("--cpu-files", type=int, default=64,
@@ -161,7 +171,21 @@ def parse():
                     help="--plan-only: free HBM per device to plan for (default: the device's)")
     ap.add_argument("--fail-rank", type=int, default=-1,
                     help="diagnostics: this rank raises during setup (every rank must then exit non-zero)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the Zipf line (--workload both), the oracle checks, the "
+                         "single-batch latency, the probed lifetime leg, the pinned-host e2e leg and the CPU "
+                         "baseline.  Without it a run sets up, warms up, times --steps steps of one workload and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the cut lists, block IDs "
+                         "and content ids of its batch) as DIR/<name>.npy (rank r > 0: DIR/rank<r>/)")
+    a = ap.parse_args()
+    if not a.full:  # the plain run: the headline workload alone, nothing measured or checked beside it
+        if a.workload == "both":
+            a.workload = "random"
+        a.no_cpu_baseline = a.no_lifetime = a.no_check = True
+        a.e2e_steps = 0
+    return a
 
 
 # ------------------------------------------------------------------ host --
@@ -520,8 +544,9 @@ def max_over_ranks(x, dist, dev, op="max"):
 
 def run_workload(a, name, eng, arenas, offs, lens, R, B, need, lanes, dist, gpu, dev, world, rank,
                  job_batch_bytes, check_threads, before_submit=None, period=1):
-    """One steady-state measurement; returns the JSON fields of its line.
-    `gpu` is this rank's device, `dev` the device of the reductions."""
+    """One steady-state measurement; returns the JSON fields of its line and
+    the per-file results of the last timed step.  `gpu` is this rank's
+    device, `dev` the device of the reductions."""
     r = steady(eng, arenas, offs, lens, R, a.steps, a.warmup, dist, gpu, before_submit,
                aliased=a.alias_depth > 0)
     el = max_over_ranks(r["el"], dist, dev)
@@ -610,7 +635,7 @@ def run_workload(a, name, eng, arenas, offs, lens, R, B, need, lanes, dist, gpu,
     if check is not None:
         out["check_vs_oracle"] = check
         out["checked_batches_per_gpu"] = n_checked
-    return out
+    return out, res
 
 
 ARENA_SLACK = 64 << 20  # per resident batch beyond its packed bytes (allocator rounding)
@@ -655,6 +680,43 @@ def residency_plan(files, file_mib, world, rank, scaling="strong", free_bytes=0,
             "offs": offs, "arena_bytes": total, "R": p["resident"], "physical_arenas": physical,
             "B": p["md5_slice"], "need": p["launches_per_batch"], "k3_period": p["k3_period"],
             "hbm_bytes": physical * (total + ARENA_SLACK), "file_bytes": fbytes}
+
+
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs writes less than 64 MB in all
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what one step returns to its caller (engine.wait: one
+    FileChunks per file of the batch), as float arrays in file order:
+      n_chunks.npy       f64 [files]       chunks of each file
+      content_types.npy  f32 [files]       entry content type (2 FileData, 3 FileChain, 0 empty)
+      content_ids.npy    f32 [files, 16]   the content block ID's bytes
+      cut_ends.npy       f64 [chunks]      chunk ends within their file, the files' lists concatenated
+      block_ids.npy      f32 [chunks, 16]  each chunk's block ID bytes, same order
+    Every value is an integer below 2^53, exact in these types.  An output
+    over the byte budget keeps a fixed seeded sample of its rows (the same rows
+    for cut_ends and block_ids), listed in file_rows.npy / chunk_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    nf = len(res)
+    cid = np.zeros((nf, 16), np.float32)
+    for i, x in enumerate(res):
+        if x.content_id:
+            cid[i] = np.frombuffer(x.content_id, np.uint8)
+    per_file = {"n_chunks": np.array([x.n_chunks for x in res], np.float64),
+                "content_types": np.array([x.content_type for x in res], np.float32), "content_ids": cid}
+    per_chunk = {"cut_ends": np.concatenate([x.cut_ends for x in res] or [np.zeros(0)]).astype(np.float64),
+                 "block_ids": np.concatenate([x.ids.reshape(-1, 16) for x in res]
+                                             or [np.zeros((0, 16))]).astype(np.float32)}
+    for tag, arrays in (("file", per_file), ("chunk", per_chunk)):
+        n = len(next(iter(arrays.values())))
+        row_bytes = sum(v[:1].nbytes for v in arrays.values()) + 8
+        keep = DUMP_MAX_BYTES // 2 // row_bytes
+        if n > keep:
+            rows = np.sort(np.random.default_rng(20240229).choice(n, keep, replace=False))
+            arrays = {k: v[rows] for k, v in arrays.items()}
+            arrays[f"{tag}_rows"] = rows.astype(np.float64)
+        for k, v in arrays.items():
+            np.save(os.path.join(path, k + ".npy"), v)
 
 
 def check_host_bytes(plan, world_on_host=1):
@@ -771,9 +833,11 @@ def setup(a, rank, world, local_world, ndev, dev_idx, dev):
     eng.apply_plan(P["lib_plan"], len(lens), sum(lens))
     k = eng.knobs()
     assert (k["md5_slice"], k["join_lag"], k["k3_period"]) == (B, lag, P["k3_period"]), k
-    for _ in range(2):  # single-batch latency (one batch alone, synchronous call), untimed
-        eng.chunk_hash_device(arenas[0].data_ptr(), offs, lens)
-    latency = eng.stage_times()
+    latency = None
+    if a.full:
+        for _ in range(2):  # single-batch latency (one batch alone, synchronous call), untimed
+            eng.chunk_hash_device(arenas[0].data_ptr(), offs, lens)
+        latency = eng.stage_times()
     return {"plan": P, "arenas": arenas, "ballast": ballast, "eng": eng, "latency": latency, "cores": cores,
             "threads": threads}
 
@@ -816,8 +880,8 @@ def e2e_leg(a, eng, arenas, offs, lens, P, lanes, dist, dev, red_dev, world, ran
 
         ae = copy.copy(a)
         ae.steps, ae.warmup = a.e2e_steps, min(a.warmup, 3)
-        r = run_workload(ae, "e2e", eng, arenas[:R_e], offs, lens, R_e, B_e, need_e, lanes, dist, dev, red_dev,
-                         world, rank, job_batch, threads, before)
+        r, _ = run_workload(ae, "e2e", eng, arenas[:R_e], offs, lens, R_e, B_e, need_e, lanes, dist, dev, red_dev,
+                            world, rank, job_batch, threads, before)
     finally:
         eng._L.hbx_free_pinned(hp)
     keep = ("value", "ms_per_step", "drain_ms", "fill_drain_gibs", "kernel_ms_per_step", "window_launches",
@@ -869,10 +933,12 @@ def run(a, S, rank, world, local_world, dist, dev, red_dev):
     for wl in workloads:
         if wl == "zipf":
             zipf_repeat = W.zipf_fill(arenas, int(offs[-1]) + lens[-1], a.seed + 4 + 7919 * rank)
-        lines[wl] = run_workload(a, wl, eng, arenas, offs, lens, R, B, need, lanes, dist, dev, red_dev,
-                                 world, rank, job_batch, threads, before, per)
+        lines[wl], last = run_workload(a, wl, eng, arenas, offs, lens, R, B, need, lanes, dist, dev, red_dev,
+                                       world, rank, job_batch, threads, before, per)
         if zipf_repeat is not None and wl == "zipf":
             lines[wl]["repeat_fraction"] = round(zipf_repeat, 4)
+        if a.dump_outputs and wl == workloads[0]:  # the headline's last timed step
+            dump_outputs(os.path.join(a.dump_outputs, f"rank{rank}") if rank else a.dump_outputs, last)
 
     life = None
     if not a.no_lifetime and a.alias_depth == 0 and not a.e2e:
@@ -930,9 +996,11 @@ def run(a, S, rank, world, local_world, dist, dev, red_dev):
                             + f"; Zipf corpus seed {a.seed + 4} + 7919 x rank"},
     }
     out.update({k: v for k, v in head.items() if k not in ("value", "ms_per_step")})
-    out["single_batch"] = {"ms": round(float(latency[4]), 3),
-                           "gibs": round(sum(lens) / GIB / (float(latency[4]) * 1e-3), 3),
-                           "stages_ms": [round(float(x), 3) for x in latency]}
+    out["full"] = a.full
+    if latency is not None:
+        out["single_batch"] = {"ms": round(float(latency[4]), 3),
+                               "gibs": round(sum(lens) / GIB / (float(latency[4]) * 1e-3), 3),
+                               "stages_ms": [round(float(x), 3) for x in latency]}
     out["cpu_baseline"] = cpu
     if life is not None:
         out["lifetime"] = life

@@ -41,7 +41,7 @@ def _torchrun(nproc, args, timeout=240):
     return json.loads(lines[-1])
 
 
-BENCH = ["bench.py", "--files", "4", "--file-mib", "16", "--steps", "6", "--warmup", "2", "--arenas", "8",
+BENCH = ["bench.py", "--full", "--files", "4", "--file-mib", "16", "--steps", "6", "--warmup", "2", "--arenas", "8",
          "--md5-slice", "32768", "--no-cpu-baseline", "--dist-backend", "gloo", "--cpu-threads", "4"]
 
 
@@ -72,7 +72,7 @@ def test_bench_configs2_full_corpus_world2():
     (hbx_plan_pipeline: lag 2, lead 3, period 1 at 32 files).  Every file of
     the last 4 batches each rank collected in the timed window, and of its
     last drained batch, is checked against the oracle."""
-    d = _torchrun(2, ["bench.py", "--gpus", "2", "--steps", "8", "--warmup", "2", "--dist-backend", "gloo",
+    d = _torchrun(2, ["bench.py", "--full", "--gpus", "2", "--steps", "8", "--warmup", "2", "--dist-backend", "gloo",
                       "--no-cpu-baseline", "--cpu-threads", "16", "--workload", "random", "--e2e-steps", "0",
                       "--no-lifetime", "--check-batches", "4"], timeout=540)
     c = d["config"]

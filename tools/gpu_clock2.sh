@@ -7,7 +7,7 @@ export HBX_AB=1  # the library honours HBX_* A/B switches only with this
 O=gpurun_out/clock2
 mkdir -p $O
 one() {  # name, HBX_HASH_CUS
-  (HBX_HASH_CUS=$2 timeout -k 10 200 python bench.py --no-cpu-baseline --steps 4000 > $O/$1.json 2> $O/$1.err; echo "bench rc=$?" >> $O/$1.err) &
+  (HBX_HASH_CUS=$2 timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 4000 > $O/$1.json 2> $O/$1.err; echo "bench rc=$?" >> $O/$1.err) &
   BP=$!
   sleep 12
   for i in $(seq 1 40); do

@@ -7,7 +7,7 @@
 # Steps:
 #   tests        the GPU suite (pytest -m gpu), as the driver runs it
 #   testsk=EXPR  a subset of the GPU suite (pytest -k EXPR)
-#   bench        the driver's command (python bench.py) -> bench20.json
+#   bench        the driver's command with every leg (python bench.py --full) -> bench20.json
 #   bench200     the same at 200 steps -> bench200.json
 #   f8 / f16 / f32   the N = 8 / 4 / 2 per-GPU shares, 20-step window -> f<n>.json
 #   f8x200       the N = 8 share over 200 steps
@@ -53,13 +53,13 @@ for step in "$@"; do
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "${step#testsk=}" > $O/gpu_tests_k.log 2>&1 \
         || { tail -40 $O/gpu_tests_k.log; exit 1; }
       tail -3 $O/gpu_tests_k.log ;;
-    bench) run_bench bench20 300 --gpus 1 --steps 20 --warmup 5 ;;  # the driver's command
-    bench200) run_bench bench200 400 --steps 200 ;;
-    f8) run_bench f8 300 --files 8 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
-    f16) run_bench f16 300 --files 16 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
-    f32) run_bench f32 300 --files 32 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
-    f8x200) run_bench f8x200 400 --files 8 --steps 200 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
-    e2e) run_bench e2e 300 --e2e --steps 40 --no-cpu-baseline ;;
+    bench) run_bench bench20 300 --full --gpus 1 --steps 20 --warmup 5 ;;  # the driver's command
+    bench200) run_bench bench200 400 --full --steps 200 ;;
+    f8) run_bench f8 300 --full --files 8 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
+    f16) run_bench f16 300 --full --files 16 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
+    f32) run_bench f32 300 --full --files 32 --steps 20 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
+    f8x200) run_bench f8x200 400 --full --files 8 --steps 200 --warmup 5 --e2e-steps 0 --no-cpu-baseline --no-lifetime ;;
+    e2e) run_bench e2e 300 --full --e2e --steps 40 --no-cpu-baseline ;;
     profile) timeout -k 10 1100 tools/profile_round.sh $TAG || exit 1 ;;
     wire)
       timeout -k 10 700 python tools/bench_wire.py --sampled > $O/wire.json 2> $O/wire.err || { tail -20 $O/wire.err; exit 1; }
@@ -101,7 +101,7 @@ for step in "$@"; do
       tail -4 $O/slow_cu.txt | cut -c1-600 ;;
     ab=*)
       kv=${step#ab=}
-      env HBX_AB=1 "$kv" timeout -k 10 300 python bench.py --e2e-steps 0 --no-cpu-baseline > $O/ab_$kv.json 2> $O/ab_$kv.err \
+      env HBX_AB=1 "$kv" timeout -k 10 300 python bench.py --full --e2e-steps 0 --no-cpu-baseline > $O/ab_$kv.json 2> $O/ab_$kv.err \
         || { echo "FAIL $step"; tail -20 $O/ab_$kv.err; exit 1; }
       summ $O/ab_$kv.json ;;
     *) echo "unknown step $step"; exit 2 ;;
