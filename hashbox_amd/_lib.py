@@ -36,6 +36,7 @@ EXPORTS = [
     "hbx_set_join_lag", "hbx_set_k3_period", "hbx_k3_wave_times", "hbx_input_after_oldest", "hbx_knobs",
     "hbx_input_fence", "hbx_set_k3_probe", "hbx_store_paths_status", "hbx_plan_pipeline", "hbx_apply_plan",
     "hbx_host_call_max",
+    "hbx_seg_next", "hbx_seg_open", "hbx_seg_close", "hbx_seg_submit_device", "hbx_store_file_seg",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -188,6 +189,11 @@ def load() -> ctypes.CDLL:
     L.hbx_store_paths_status.argtypes = [P, U64, P, P, P, P, P, P, P, P, ctypes.c_uint32, U64, P, P, P, P, P, P]
     L.hbx_plan_pipeline.argtypes = [P, ctypes.POINTER(PlanRequest), ctypes.POINTER(PipelinePlan)]
     L.hbx_apply_plan.argtypes = [P, ctypes.POINTER(PipelinePlan), U64, U64]
+    L.hbx_seg_next.argtypes = [U64, U64, U64, PU64, PU64]
+    L.hbx_seg_open.argtypes = [P, U64, ctypes.POINTER(P)]
+    L.hbx_seg_close.argtypes = [P, P]
+    L.hbx_seg_submit_device.argtypes = [P, U64, P, P, P, P, P, P, P, P, P]
+    L.hbx_store_file_seg.argtypes = [P, ctypes.c_char_p, U64, U64, ctypes.c_uint32, P, P, U64, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

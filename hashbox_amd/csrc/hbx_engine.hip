@@ -124,6 +124,26 @@ ResLayout res_layout(uint64_t n_files, uint64_t total_cap) {
   return r;
 }
 
+}  // namespace
+
+// One file streamed in segments (hbx_seg_open).  The carry word lives in
+// device memory (a slot of hbx_ctx::seg_words): K2 of segment j stores the
+// chain's resume point there and K2 of segment j+1 loads it, so no segment
+// waits for the host.  The host side keeps what the final content id needs.
+struct hbx_seg {
+  uint64_t file_len = 0;
+  uint64_t* d_carry = nullptr;
+  uint64_t end = 0;           // file offset where the latest submitted segment ends
+  bool any = false;           // a segment has been submitted
+  bool final_sent = false;    // the final segment has been submitted
+  uint32_t inflight = 0;      // submitted segments not yet collected
+  std::vector<uint8_t> ids;   // the file's chunk ids collected so far (the chain block's links)
+  bool keep_cuts = false;     // hbx_store_file_seg: collect the cut ends here too
+  std::vector<uint64_t> cuts;
+};
+
+namespace {
+
 // One submitted batch.  Its device buffers live until its results are
 // collected: K3 writes BlockIDs into d_ids across several launches when the
 // MD5 stage is time-sliced.
@@ -154,6 +174,12 @@ struct Batch {
   const uint8_t* v_expect = nullptr;
   uint8_t* v_ok = nullptr;
   uint64_t* v_nbad = nullptr;
+  // a batch of file segments (hbx_seg_submit_device): entry f is the next
+  // segment of segs[f], file bytes [seg_off[f], seg_off[f] + len); K2 is the
+  // segment form, K4 is skipped, and the collect adds seg_off to the cuts
+  std::vector<hbx_seg*> segs;
+  std::vector<uint64_t> seg_off;
+  std::vector<uint8_t> seg_final;
   // K1 start | K1 end | K2r end | plan+K3 end (first) | results ready | K2 end (lean marks)
   hipEvent_t ev[6] = {};
   void release() {
@@ -341,6 +367,17 @@ struct hbx_ctx {
   std::vector<DevBuf> d_ring;  // hbx_store_paths: device arenas of the batches in flight
   double io_s[3] = {0, 0, 0};  // hbx_store_paths: reading files | waiting for an arena | waiting for a copy
 
+  // hbx_seg_*: open segmented files, their carry words (8 bytes each, handed
+  // out from 4 KiB device blocks and reused: closing a file frees no device
+  // memory, which would wait for the device), the final chain block's
+  // message and the stream its block id is computed on (created by the first
+  // hbx_seg_open; beside, never inside, the pipeline's four streams)
+  std::vector<hbx_seg*> segs_open;
+  std::vector<DevBuf> seg_words;
+  std::vector<uint64_t*> seg_words_free;
+  hipStream_t sstream = nullptr;
+  DevBuf d_segmsg;
+
   std::deque<Batch*> pending;  // submitted, not yet collected (FIFO)
   std::vector<Batch*> pool;
   // A HIP error after a batch's device work was enqueued leaves chains of it
@@ -499,6 +536,9 @@ Batch* acquire_batch(hbx_ctx* c) {
   b->v_expect = nullptr;
   b->v_ok = nullptr;
   b->v_nbad = nullptr;
+  b->segs.clear();
+  b->seg_off.clear();
+  b->seg_final.clear();
   return b;
 }
 
@@ -567,7 +607,9 @@ int finalize_batch(hbx_ctx* c, Batch* b) {
   if (b->n) {
     const uint64_t n = b->n;
     const uint64_t* d_cb = b->d_meta.as<uint64_t>() + 3 * n;
-    {
+    // (a segment's content id is the whole file's: the collect of the final
+    // segment computes it, collect_segments)
+    if (b->segs.empty()) {
       StageTimer t(c, s, 4);
       hipLaunchKernelGGL(hbx_k4_content_id, dim3((uint32_t)n), dim3(64), 0, s,
                          (uint32_t)n, d_cb, b->count_d(), b->ids_d(), reinterpret_cast<uint32_t*>(b->res(b->rl.cid)),
@@ -978,7 +1020,8 @@ inline uint64_t scan_iters(uint64_t N) {  // K1 iterations of a file (0: no spli
 // removes it again (submit_abort), so a failed submit leaves no pending batch.
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
-                       const uint64_t* caps, hbx_file_summary* sums, uint32_t budget);
+                       const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
+                       const uint64_t* seg_offs);
 }  // namespace
 // hbx_reserve with the context's lock already held (defined beside it, inside
 // the C-ABI block; not exported)
@@ -987,15 +1030,18 @@ extern "C" __attribute__((visibility("hidden"))) int reserve_locked(hbx_ctx* c, 
 namespace {
 int submit_batch(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                  const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
-                 const uint64_t* caps, hbx_file_summary* sums, uint32_t budget) {
+                 const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs = nullptr,
+                 const uint64_t* seg_offs = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
-  const int rc = submit_batch_timed(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, budget);
+  const int rc = submit_batch_timed(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, budget, segs,
+                                    seg_offs);
   c->max_submit_ms = std::max(c->max_submit_ms, ms_since(t0));
   return rc;
 }
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
-                       const uint64_t* caps, hbx_file_summary* sums, uint32_t budget) {
+                       const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
+                       const uint64_t* seg_offs) {
   g_slow.mark(0);
   g_slow.clear();
   if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
@@ -1011,6 +1057,12 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
   b->out_base.assign(out_base, out_base + n);
   b->capv.assign(caps, caps + n);
   b->cut_base.resize(n);
+  if (segs) {  // (validated by the caller: seg_submit)
+    b->segs.assign(segs, segs + n);
+    b->seg_off.assign(seg_offs, seg_offs + n);
+    b->seg_final.resize(n);
+    for (uint64_t f = 0; f < n; f++) b->seg_final[f] = seg_offs[f] + lens[f] == segs[f]->file_len;
+  }
   c->h_slice_base.resize(n);
   c->h_tiles.clear();
   uint64_t slices = 0, tcaps = 0, longest = 0, total_iters = 0;
@@ -1043,8 +1095,9 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
   const uint64_t lb = launch_budget(c, budget);  // a K3 period multiplies the slice
   b->need = budget == kBudgetAll ? 1u : (uint32_t)std::max<uint64_t>(1, (nfull + lb - 1) / lb);
   const uint64_t nt = c->h_tiles.size();
-  // meta block: off | len | slice_base | cut_base | tiles
-  const size_t meta_bytes = n * 8 * 4 + nt * sizeof(uint4);
+  // meta block: off | len | slice_base | cut_base | tiles, and for segments
+  // | carry address | seg_off | final | first start (written by K2)
+  const size_t meta_bytes = n * 8 * 4 + nt * sizeof(uint4) + (segs ? n * 8 * 4 : 0);
   const int slot = c->ssum_slot;
   g_slow.mark(1);
   if (n) {  // every allocation first: the batch is not in the FIFO yet
@@ -1093,6 +1146,15 @@ int submit_batch_launch(hbx_ctx* c, Batch* b, const void* d_arena, uint64_t n, c
   std::memcpy(hm + 2 * n, c->h_slice_base.data(), n * 8);
   std::memcpy(hm + 3 * n, b->cut_base.data(), n * 8);
   if (nt) std::memcpy(hm + 4 * n, c->h_tiles.data(), nt * sizeof(uint4));
+  const bool seg = !b->segs.empty();
+  const size_t seg_at = 4 * n + 2 * nt;  // in u64 units
+  if (seg)
+    for (uint64_t f = 0; f < n; f++) {
+      hm[seg_at + f] = reinterpret_cast<uint64_t>(b->segs[f]->d_carry);
+      hm[seg_at + n + f] = b->seg_off[f];
+      hm[seg_at + 2 * n + f] = b->seg_final[f];
+      hm[seg_at + 3 * n + f] = 0;
+    }
   c->ssum_slot ^= 1;
   DevBuf& ssum = c->d_ssum[slot];
 
@@ -1158,11 +1220,22 @@ int submit_batch_launch(hbx_ctx* c, Batch* b, const void* d_arena, uint64_t n, c
   // K2 on the cut stream: the scan stream goes straight on with the next
   // batch's K1 (into the other summary slot)
   if (s2 != s) HBX_TRY(c, hipStreamWaitEvent(s2, b->ev[1], 0));
+  // Segments: the carry of a file goes from this K2 to the K2 of its next
+  // segment through device memory, so the two must run in submit order.
+  // They do: every K2 of a context is launched here, on the cut stream, and
+  // that stream changes only while no batch is pending (ensure_cut_stream).
+  uint64_t* d_first = seg ? b->d_meta.as<uint64_t>() + seg_at + 3 * n : nullptr;
   {
     StageTimer t(c, s2, 1, !lean);
-    hipLaunchKernelGGL(hbx_k2_cut_chain, dim3((uint32_t)n), dim3(64), 0, s2, arena, d_off, d_len,
-                       d_sb, ssum.as<uint2>(), d_cb, b->cuts_d(), b->count_d(),
-                       lean ? b->d_fcnt.as<uint32_t>() : nullptr);
+    if (seg)
+      hipLaunchKernelGGL(hbx_k2s_cut_chain_seg, dim3((uint32_t)n), dim3(64), 0, s2, arena, d_off, d_len,
+                         d_sb, ssum.as<uint2>(), d_cb, b->cuts_d(), b->count_d(),
+                         lean ? b->d_fcnt.as<uint32_t>() : nullptr, d_off + seg_at, d_off + seg_at + n,
+                         d_off + seg_at + 2 * n, d_first);
+    else
+      hipLaunchKernelGGL(hbx_k2_cut_chain, dim3((uint32_t)n), dim3(64), 0, s2, arena, d_off, d_len,
+                         d_sb, ssum.as<uint2>(), d_cb, b->cuts_d(), b->count_d(),
+                         lean ? b->d_fcnt.as<uint32_t>() : nullptr);
   }
   HBX_TRY(c, hipGetLastError());
   if (lean) {  // the summary slot's next writer (K1, this stream) follows in order: no ssum_free
@@ -1176,7 +1249,7 @@ int submit_batch_launch(hbx_ctx* c, Batch* b, const void* d_arena, uint64_t n, c
   if (!lean) HBX_TRY(c, hipMemsetAsync(b->d_fcnt.p, 0, 4, s2));
   hipLaunchKernelGGL(hbx_k2r_new_chains, dim3((uint32_t)((n * kPlanLanesPerFile + 255) / 256)), dim3(256), 0, s2,
                      (uint32_t)n, arena, d_off, d_cb, b->cuts_d(), b->count_d(), b->ids_d(), b->d_run.as<Chain>(), b->d_fresh.as<OrderEntry>(),
-                     b->d_fcnt.as<uint32_t>());
+                     b->d_fcnt.as<uint32_t>(), static_cast<const uint64_t*>(d_first));
   HBX_TRY(c, hipGetLastError());
   // the plan this batch joins waits for ev[2] (plan_launch), so with a join
   // lag of 2 the scan stream never waits for this K2.  Lean marks with the
@@ -1276,6 +1349,104 @@ int submit_verify_launch(hbx_ctx* c, Batch* b, const uint8_t* arena, uint64_t n,
   return HBX_OK;
 }
 
+// MD5(BE32(n_links) || links || BE32(len) || data) on stream `s`, the message
+// staged in `buf` (HashboxBlock.HashData, block.go:96-111): hbx_block_id, and
+// the FileChainBlock id of a segmented file.  Waits for `s` only.  A message
+// of a block or more goes through hbx_k5r_md5_run, a shorter one through K5.
+int block_id_on(hbx_ctx* c, hipStream_t s, DevBuf& buf, const uint8_t* links, uint32_t n_links,
+                const uint8_t* data, uint64_t len, uint8_t out[16]) {
+  const uint64_t n = 8 + 16ull * n_links + len;
+  std::vector<uint8_t> msg(n);
+  auto be32 = [](uint8_t* b, uint32_t v) {
+    b[0] = (uint8_t)(v >> 24);
+    b[1] = (uint8_t)(v >> 16);
+    b[2] = (uint8_t)(v >> 8);
+    b[3] = (uint8_t)v;
+  };
+  be32(msg.data(), n_links);
+  if (n_links) std::memcpy(msg.data() + 4, links, 16ull * n_links);
+  be32(msg.data() + 4 + 16ull * n_links, (uint32_t)len);
+  if (len) std::memcpy(msg.data() + 8 + 16ull * n_links, data, len);
+  HBX_TRY(c, buf.ensure(n + 16 + 128));  // (+128: hbx_k5r_md5_run reads up to 63 bytes past the message)
+  uint8_t* dm = buf.as<uint8_t>();
+  HBX_TRY(c, hipMemcpyAsync(dm + 16, msg.data(), n, hipMemcpyHostToDevice, s));
+  if (n >= 64)
+    hipLaunchKernelGGL(hbx_k5r_md5_run, dim3(1), dim3(64), 0, s, dm + 16, (uint32_t)n,
+                       reinterpret_cast<uint32_t*>(dm));
+  else
+    hipLaunchKernelGGL(hbx_k5_md5_raw, dim3(1), dim3(64), 0, s, dm + 16, (uint32_t)n,
+                       reinterpret_cast<uint32_t*>(dm));
+  HBX_TRY(c, hipGetLastError());
+  HBX_TRY(c, hipMemcpyAsync(out, dm, 16, hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+// entry.ContentType / ContentBlockID of a segmented file whose final segment
+// has been collected (store.go:187-196), from the chunk ids gathered in its
+// handle: one chunk = that chunk's id, more = the id of the FileChainBlock
+// with the ids as links, hashed on the device (K5) on the segment stream,
+// beside the batches still in flight.
+int seg_file_summary(hbx_ctx* c, hbx_seg* h, hbx_file_summary* sum) {
+  const uint64_t k = h->ids.size() / 16;
+  std::memset(sum->content_id, 0, 16);
+  sum->content_type = 0;
+  if (k == 0) return HBX_OK;
+  if (k == 1) {
+    std::memcpy(sum->content_id, h->ids.data(), 16);
+    sum->content_type = HBX_CONTENT_FILE_DATA;
+    return HBX_OK;
+  }
+  // the block's data is 8 + 32k bytes behind BE32(len); the whole message
+  // (16 + 48k bytes) must also fit the MD5 kernel's 32-bit length
+  const uint64_t body = 8 + 32 * k;
+  if (body > 0xFFFFFFFFull || 16 + 48 * k + 16 + 128 > 0xFFFFFFFFull)
+    return c->fail(HBX_ERR_CAPACITY, "file has too many chunks for one FileChainBlock (" + std::to_string(k) + ")");
+  std::vector<uint8_t> blk(body);
+  uint64_t wrote = 0;
+  if (hbx_chain_block_serialize(h->ids.data(), nullptr, (uint32_t)k, blk.data(), body, &wrote) != HBX_OK || wrote != body)
+    return c->fail(HBX_ERR_STATE, "chain block serialization (internal)");
+  int rc = block_id_on(c, c->sstream, c->d_segmsg, h->ids.data(), (uint32_t)k, blk.data(), body, sum->content_id);
+  if (rc) return rc;
+  sum->content_type = HBX_CONTENT_FILE_CHAIN;
+  return HBX_OK;
+}
+
+// A collected batch of segments: cut ends become absolute file offsets, the
+// chunk ids join their file's handle, and a final segment's summary carries
+// the whole file's content type and id.
+int collect_segments(hbx_ctx* c, Batch* b) {
+  const ResLayout& rl = b->rl;
+  const uint8_t* hr = b->h_res.as<uint8_t>();
+  const uint32_t* counts = reinterpret_cast<const uint32_t*>(hr + rl.counts);
+  const uint64_t* cuts = reinterpret_cast<const uint64_t*>(hr + rl.cuts);
+  const uint8_t* hid = hr + rl.ids;
+  int rc = HBX_OK;
+  for (uint64_t f = 0; f < b->n; f++) {
+    hbx_seg* h = b->segs[f];
+    const uint64_t k = counts[f], ib = b->cut_base[f], so = b->seg_off[f];
+    h->inflight--;
+    h->ids.insert(h->ids.end(), hid + 16 * ib, hid + 16 * (ib + k));
+    if (h->keep_cuts)
+      for (uint64_t i = 0; i < k; i++) h->cuts.push_back(so + cuts[ib + i]);
+    hbx_file_summary sum{};
+    sum.n_chunks = (uint32_t)k;
+    if (b->seg_final[f]) {
+      const int r2 = seg_file_summary(c, h, &sum);
+      if (r2 && !rc) rc = r2;
+    }
+    if (b->sums) b->sums[f] = sum;
+    if (k > b->capv[f]) {  // (not reached: the submit checked caps against hbx_max_chunks)
+      rc = c->fail(HBX_ERR_CAPACITY, "output capacity too small for segment " + std::to_string(f));
+      continue;
+    }
+    if (b->cut_ends)
+      for (uint64_t i = 0; i < k; i++) b->cut_ends[b->out_base[f] + i] = so + cuts[ib + i];
+    if (b->ids) std::memcpy(b->ids + 16 * b->out_base[f], hid + 16 * ib, k * 16);
+  }
+  return rc;
+}
+
 // Scatter a collected batch's pinned results into the caller's arrays.
 int collect_batch(hbx_ctx* c, Batch* b) {
   const uint64_t n = b->n;
@@ -1300,8 +1471,8 @@ int collect_batch(hbx_ctx* c, Batch* b) {
   const uint8_t* hid = hr + rl.ids;
   const uint8_t* cid = hr + rl.cid;
   const int32_t* ctype = reinterpret_cast<const int32_t*>(hr + rl.ctype);
-  int rc = HBX_OK;
-  for (uint64_t f = 0; f < n; f++) {
+  int rc = b->segs.empty() ? HBX_OK : collect_segments(c, b);
+  for (uint64_t f = 0; f < n && b->segs.empty(); f++) {
     const uint64_t k = counts[f];
     const uint64_t ib = b->cut_base[f];
     if (b->sums) {
@@ -1588,6 +1759,13 @@ void hbx_ctx_destroy(hbx_ctx* c) {
     if (z.done) (void)hipEventDestroy(z.done);
     if (z.stream) (void)hipStreamDestroy(z.stream);
   }
+  if (c->sstream) {
+    (void)hipStreamSynchronize(c->sstream);
+    (void)hipStreamDestroy(c->sstream);
+  }
+  for (hbx_seg* h : c->segs_open) delete h;
+  for (DevBuf& d : c->seg_words) d.release();
+  c->d_segmsg.release();
   c->h_k3t.release();
   c->h_probe.release();
   c->h_err.release();
@@ -1820,7 +1998,7 @@ int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes)
   const uint64_t caps = bytes / HBX_MIN_BLOCK_SIZE + files;  // >= sum of max_chunks over the files
   const uint64_t tiles = bytes / ((uint64_t)(c->tile_iters ? c->tile_iters : kTileItersMin) * HBX_MIN_BLOCK_SIZE) + files;
   const uint64_t slices = bytes / kSlice + files;
-  const size_t meta_bytes = files * 8 * 4 + tiles * sizeof(uint4);
+  const size_t meta_bytes = files * 8 * 8 + tiles * sizeof(uint4);  // (8: a batch of segments)
   int rc = HBX_OK;
   for (int t = 0; t < 2 && !rc; t++) rc = ensure_shared(c, c->d_ssum[t], (slices + 1) * sizeof(uint2));
   if (!rc) rc = ensure_shared(c, c->d_plan, 2 * kPlanBins * sizeof(uint32_t));
@@ -1900,6 +2078,106 @@ int hbx_pending(hbx_ctx* c) {
   return (int)c->pending.size();
 }
 
+// ---- files larger than a batch: segments (DESIGN.md "Segmented files") ----
+int hbx_seg_next(uint64_t file_len, uint64_t seg_bytes, uint64_t prev_end, uint64_t* off, uint64_t* len) {
+  if (!off || !len) return HBX_ERR_ARG;
+  if (seg_bytes < HBX_SEG_MIN_BYTES || seg_bytes % HBX_ARENA_ALIGN) return HBX_ERR_ARG;
+  if (prev_end > 0 && (prev_end >= file_len || prev_end < HBX_SEG_OVERLAP)) return HBX_ERR_ARG;  // nothing is left
+  const uint64_t o = prev_end ? prev_end - HBX_SEG_OVERLAP : 0;
+  *off = o;
+  *len = std::min(seg_bytes, file_len - o);
+  return HBX_OK;
+}
+
+int hbx_seg_open(hbx_ctx* c, uint64_t file_len, hbx_seg** out) {
+  if (!c || !out) return HBX_ERR_ARG;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  HBX_TRY(c, hipSetDevice(c->device));
+  if (!c->sstream) HBX_TRY(c, hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
+  if (c->seg_words_free.empty()) {  // 512 more carry words
+    c->seg_words.emplace_back();
+    DevBuf& blk = c->seg_words.back();
+    if (int rc = c->hip(blk.ensure(4096), "carry words")) {
+      c->seg_words.pop_back();
+      return rc;
+    }
+    for (int i = 511; i >= 0; i--) c->seg_words_free.push_back(blk.as<uint64_t>() + i);
+  }
+  hbx_seg* h = new hbx_seg();
+  h->file_len = file_len;
+  h->d_carry = c->seg_words_free.back();  // (never read before a K2 of this file has written it)
+  c->seg_words_free.pop_back();
+  c->segs_open.push_back(h);
+  *out = h;
+  return HBX_OK;
+}
+
+int hbx_seg_close(hbx_ctx* c, hbx_seg* h) {
+  if (!c || !h) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  auto it = std::find(c->segs_open.begin(), c->segs_open.end(), h);
+  if (it == c->segs_open.end()) return c->fail(HBX_ERR_ARG, "not an open segmented file of this context");
+  // (a broken context never collects: its batches are parked until destroy)
+  if (h->inflight && !c->broken) return c->fail(HBX_ERR_STATE, "a segment of the file is still pending");
+  c->segs_open.erase(it);
+  // with nothing pending every K2 that touched the word has completed
+  if (!h->inflight) c->seg_words_free.push_back(h->d_carry);
+  delete h;
+  return HBX_OK;
+}
+
+namespace {
+// Validate one batch of segments against their handles and enqueue it; the
+// handles advance only once the batch is in the FIFO.
+int seg_submit(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena, const uint64_t* arena_offs,
+               const uint64_t* seg_lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
+               const uint64_t* caps, hbx_file_summary* sums, uint32_t budget) {
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  std::vector<uint64_t> seg_offs(n);
+  for (uint64_t f = 0; f < n; f++) {
+    hbx_seg* h = segs[f];
+    if (!h || std::find(c->segs_open.begin(), c->segs_open.end(), h) == c->segs_open.end())
+      return c->fail(HBX_ERR_ARG, "segment " + std::to_string(f) + ": not an open segmented file of this context");
+    for (uint64_t g = 0; g < f; g++)
+      if (segs[g] == h) return c->fail(HBX_ERR_ARG, "two segments of one file in a batch");
+    if (h->final_sent) return c->fail(HBX_ERR_STATE, "segment " + std::to_string(f) + ": the file's final segment was already submitted");
+    const uint64_t off = h->any ? h->end - HBX_SEG_OVERLAP : 0, L = seg_lens[f];
+    seg_offs[f] = off;
+    if (L > h->file_len - off) return c->fail(HBX_ERR_ARG, "segment " + std::to_string(f) + ": longer than the rest of the file");
+    const bool final = off + L == h->file_len;
+    if (!final && (L < HBX_SEG_MIN_BYTES || L % HBX_ARENA_ALIGN))
+      return c->fail(HBX_ERR_ARG, "segment " + std::to_string(f) +
+                                      ": a non-final segment is at least HBX_SEG_MIN_BYTES and a multiple of HBX_ARENA_ALIGN");
+    if (caps[f] < max_chunks(L))
+      return c->fail(HBX_ERR_CAPACITY, "segment " + std::to_string(f) + ": caps below hbx_max_chunks(seg_len)");
+  }
+  int rc = submit_batch(c, d_arena, n, arena_offs, seg_lens, cut_ends, ids, out_base, caps, sums, budget, segs,
+                        seg_offs.data());
+  if (rc) return rc;
+  for (uint64_t f = 0; f < n; f++) {
+    hbx_seg* h = segs[f];
+    h->any = true;
+    h->end = seg_offs[f] + seg_lens[f];
+    h->final_sent = h->end == h->file_len;
+    h->inflight++;
+  }
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_seg_submit_device(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena,
+                          const uint64_t* arena_offs, const uint64_t* seg_lens, uint64_t* cut_ends, uint8_t* ids,
+                          const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums) {
+  if (!c) return HBX_ERR_ARG;
+  if (!n || !segs || !d_arena || !arena_offs || !seg_lens || !out_base || !caps) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  HBX_TRY(c, hipSetDevice(c->device));
+  return seg_submit(c, n, segs, d_arena, arena_offs, seg_lens, cut_ends, ids, out_base, caps, sums,
+                    c->md5_slice ? c->md5_slice : kBudgetAll);
+}
+
 int hbx_chunk_hash_batch(hbx_ctx* c, uint64_t n, const uint8_t* const* datas,
                          const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids,
                          const uint64_t* out_base, const uint64_t* caps,
@@ -1945,27 +2223,8 @@ int hbx_block_id(hbx_ctx* c, const uint8_t* links, uint32_t n_links, const uint8
   std::lock_guard<std::mutex> g(c->mu);
   HBX_TRY(c, hipSetDevice(c->device));
   const uint64_t n = 8 + 16ull * n_links + len;
-  if (n + 16 > 0xFFFFFFFFull) return HBX_ERR_ARG;
-  std::vector<uint8_t> msg(n);
-  auto be32 = [](uint8_t* b, uint32_t v) {
-    b[0] = (uint8_t)(v >> 24);
-    b[1] = (uint8_t)(v >> 16);
-    b[2] = (uint8_t)(v >> 8);
-    b[3] = (uint8_t)v;
-  };
-  be32(msg.data(), n_links);
-  if (n_links) std::memcpy(msg.data() + 4, links, 16ull * n_links);
-  be32(msg.data() + 4 + 16ull * n_links, (uint32_t)len);
-  if (len) std::memcpy(msg.data() + 8 + 16ull * n_links, data, len);
-  HBX_TRY(c, c->d_msg.ensure(n + 16));
-  uint8_t* dm = c->d_msg.as<uint8_t>();
-  HBX_TRY(c, hipMemcpyAsync(dm + 16, msg.data(), n, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(hbx_k5_md5_raw, dim3(1), dim3(64), 0, c->stream, dm + 16, (uint32_t)n,
-                     reinterpret_cast<uint32_t*>(dm));
-  HBX_TRY(c, hipGetLastError());
-  HBX_TRY(c, hipMemcpyAsync(out, dm, 16, hipMemcpyDeviceToHost, c->stream));
-  HBX_TRY(c, hipStreamSynchronize(c->stream));
-  return HBX_OK;
+  if (n + 16 + 128 > 0xFFFFFFFFull) return HBX_ERR_ARG;
+  return block_id_on(c, c->stream, c->d_msg, links, n_links, data, len, out);
 }
 
 // MD5(data) on the device (K5 over the raw message): core.Hash (core.go:46-48),
@@ -2375,6 +2634,16 @@ int hbx_store_paths_zcb(hbx_ctx* c, uint64_t n, const char* const* paths, const 
 }
 
 namespace {
+// Device arenas of the disk paths' ring (2..64) for a per-submit slice
+// `budget`: a batch's chains join the launch join_lag submits later (up to
+// P - 1 more with a K3 period P) and need ceil(nfull / (P x budget)) launches
+// P submits apart, so this many arenas keep the collect from forcing a drain.
+size_t ring_depth(const hbx_ctx* c, uint32_t budget) {
+  const uint64_t nfull_max = (HBX_MAX_BLOCK_SIZE + 8ull) >> 6;
+  const uint64_t lb = launch_budget(c, budget), per = std::max<uint32_t>(1, c->k3_period);
+  return budget == kBudgetAll ? 2 : (size_t)std::min<uint64_t>(64, (nfull_max + lb - 1) / lb * per + c->join_lag + per);
+}
+
 int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
                      uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
                      hbx_file_summary* sums, uint32_t io_threads, uint64_t batch_bytes, const ZOut& z,
@@ -2390,13 +2659,7 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
   // MD5 chains.  A pinned slot is free once its copy has completed, a device
   // arena once its batch has been collected.
   const uint32_t budget = c->md5_slice ? c->md5_slice : kBudgetAll;
-  const uint64_t nfull_max = (HBX_MAX_BLOCK_SIZE + 8ull) >> 6;
-  // a batch's chains join the launch join_lag submits later (up to P - 1
-  // more with a K3 period P) and need ceil(nfull / (P x budget)) launches P
-  // submits apart, so this many arenas keep the collect from forcing a drain
-  const uint64_t lb = launch_budget(c, budget), per = std::max<uint32_t>(1, c->k3_period);
-  const size_t depth = budget == kBudgetAll ? 2 : (size_t)std::min<uint64_t>(
-      64, (nfull_max + lb - 1) / lb * per + c->join_lag + per);
+  const size_t depth = ring_depth(c, budget);
   if (c->d_ring.size() < depth) c->d_ring.resize(depth);
   // size every staging buffer once, for the largest batch this call forms
   // (growing one later would re-pin host memory or drain the streams)
@@ -2584,6 +2847,151 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
   return rc;
 }
 }  // namespace
+
+namespace {
+// Read file bytes [off, off + len) of `fd` into dst with `threads` ranged
+// preads (pieces of whole MiB).  0, or HBX_ERR_IO with the reason in err.
+int read_range(int fd, const char* path, uint64_t off, uint64_t len, uint8_t* dst, uint32_t threads,
+               std::string& err) {
+  const uint64_t piece = std::max<uint64_t>(1ull << 20, ((len + threads - 1) / std::max(1u, threads) + 0xFFFFFull) & ~0xFFFFFull);
+  const uint64_t np = (len + piece - 1) / piece;
+  std::atomic<uint64_t> next{0};
+  std::atomic<int> failed{0};
+  std::mutex emu;
+  auto worker = [&]() {
+    for (;;) {
+      const uint64_t i = next.fetch_add(1);
+      if (i >= np || failed.load()) return;
+      const uint64_t a = i * piece, want = std::min(piece, len - a);
+      uint64_t got = 0;
+      int e = 0;
+      while (got < want) {
+        const ssize_t r = ::pread(fd, dst + a + got, want - got, (off_t)(off + a + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          e = r < 0 ? errno : 0;  // 0: end of file before the stated size
+          break;
+        }
+        got += (uint64_t)r;
+      }
+      if (got == want) continue;
+      failed.store(1);
+      std::lock_guard<std::mutex> g(emu);
+      err = std::string("cannot read ") + std::to_string(want) + " bytes at " + std::to_string(off + a) + " of " + path +
+            ": " + (e ? std::string(std::strerror(e)) : "end of file after " + std::to_string(got) + " bytes");
+      return;
+    }
+  };
+  const uint32_t nt = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(threads, np));
+  std::vector<std::thread> pool;
+  for (uint32_t t = 1; t < nt; t++) pool.emplace_back(worker);
+  worker();
+  for (auto& t : pool) t.join();
+  return failed.load() ? HBX_ERR_IO : HBX_OK;
+}
+}  // namespace
+
+int hbx_store_file_seg(hbx_ctx* c, const char* path, uint64_t file_len, uint64_t seg_bytes, uint32_t io_threads,
+                       uint64_t* cut_ends, uint8_t* ids, uint64_t cap, hbx_file_summary* summary) {
+  if (!c || !path || !summary || (cap && (!cut_ends || !ids))) return HBX_ERR_ARG;
+  if (seg_bytes < HBX_SEG_MIN_BYTES || seg_bytes % HBX_ARENA_ALIGN) return HBX_ERR_ARG;
+  hbx_seg* h = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  }
+  int rc = hbx_seg_open(c, file_len, &h);
+  if (rc) return rc;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    h->keep_cuts = true;
+    rc = [&]() -> int {
+      if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+      HBX_TRY(c, hipSetDevice(c->device));
+      for (hipEvent_t& e : c->h2d_done)
+        if (!e) HBX_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      // Every buffer is sized by the segment, never by the file: two pinned
+      // slots and `depth` device arenas of min(seg_bytes, file_len) + 64 KiB
+      const uint32_t budget = c->md5_slice ? c->md5_slice : kBudgetAll;
+      const size_t depth = ring_depth(c, budget);
+      const uint64_t slot_bytes = std::min(seg_bytes, file_len) + 65536;
+      if (c->d_ring.size() < depth) c->d_ring.resize(depth);
+      for (PinBuf& p : c->h_read) HBX_TRY(c, p.ensure(slot_bytes));
+      for (size_t i = 0; i < depth; i++)
+        if (int r0 = ensure_shared(c, c->d_ring[i], slot_bytes)) return r0;
+      if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, 1, slot_bytes)) return r0;
+      const int fd = file_len ? ::open(path, O_RDONLY | O_CLOEXEC) : -1;
+      if (file_len && fd < 0)
+        return c->fail(HBX_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+      auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+      bool slot_used[2] = {false, false};
+      const uint64_t zero = 0;
+      uint64_t prev_end = 0, k = 0;
+      int r = HBX_OK;
+      // Segment k is read into pinned slot k % 2 while earlier segments copy
+      // and hash; reading never waits for a cut: the chain's resume point goes
+      // from segment to segment on the device (hbx_k2s_cut_chain_seg).
+      for (bool more = true; more && r == HBX_OK; k++) {
+        uint64_t off = 0, len = 0;
+        if ((r = hbx_seg_next(file_len, seg_bytes, prev_end, &off, &len))) {
+          r = c->fail(r, "segment layout (internal)");
+          break;
+        }
+        prev_end = off + len;
+        more = prev_end < file_len;
+        const int p = (int)(k & 1);
+        DevBuf& arena = c->d_ring[k % depth];
+        const double t0 = now();
+        if (c->pending.size() >= depth && (r = wait_oldest(c))) break;  // frees arena k % depth
+        const double t1 = now();
+        if (slot_used[p] && (r = c->hip(hipEventSynchronize(c->h2d_done[p]), "h2d wait"))) break;
+        const double t2 = now();
+        if (len) r = read_range(fd, path, off, len, c->h_read[p].as<uint8_t>(), std::max(1u, io_threads), c->err);
+        c->io_s[0] += now() - t2;
+        c->io_s[1] += t1 - t0;
+        c->io_s[2] += t2 - t1;
+        if (r) break;
+        if (len) {
+          const auto tc = std::chrono::steady_clock::now();
+          if ((r = c->hip(hipMemcpyAsync(arena.p, c->h_read[p].p, len, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync")))
+            break;
+          c->max_copy_ms = std::max(c->max_copy_ms, ms_since(tc));
+          if ((r = c->hip(hipEventRecord(c->h2d_done[p], c->stream), "hipEventRecord"))) break;
+          slot_used[p] = true;
+        }
+        const uint64_t scap = max_chunks(len);
+        r = seg_submit(c, 1, &h, arena.p, &zero, &len, nullptr, nullptr, &zero, &scap, summary, budget);
+      }
+      if (fd >= 0) ::close(fd);
+      // collect everything in flight, also after a failure
+      const double td = now();
+      while (!c->pending.empty()) {
+        const std::string keep = c->err;
+        const int r2 = wait_oldest(c);
+        if (r == HBX_OK) r = r2;
+        else c->err = keep;
+      }
+      c->io_s[1] += now() - td;
+      return r;
+    }();
+    if (rc == HBX_OK) {
+      // (`summary` was written by every segment's collect; the final one's,
+      // collected last, carries the file's content type and id)
+      const uint64_t kk = h->cuts.size();
+      summary->n_chunks = (uint32_t)kk;
+      if (kk > cap) {
+        rc = c->fail(HBX_ERR_CAPACITY, "output capacity too small for the file (" + std::to_string(kk) + " chunks)");
+      } else if (kk) {
+        std::memcpy(cut_ends, h->cuts.data(), kk * 8);
+        std::memcpy(ids, h->ids.data(), kk * 16);
+      }
+    }
+  }
+  const std::string keep = c->err;
+  (void)hbx_seg_close(c, h);
+  if (rc) c->err = keep;
+  return rc;
+}
 
 int hbx_host_call_max(hbx_ctx* c, double ms[2], int reset) {
   if (!c || !ms) return HBX_ERR_ARG;

@@ -433,12 +433,25 @@ __device__ void slice_argmax(const uint8_t* fb, uint64_t N, uint64_t j, uint32_t
 // slices of a MAX-sized candidate range in one round
 constexpr int kK2Loads = 32;
 
-extern "C" __global__ __launch_bounds__(64) void hbx_k2_cut_chain(
+// The cut chain of one file (SEG = false), or of one segment of a file
+// streamed in overlapping segments (SEG = true): the arena then holds file
+// bytes [seg_off, seg_off + N), the chain resumes at the chunk start the
+// file's previous segment left in *carry (an absolute file offset; a first
+// segment, seg_off = 0, starts at 0 and does not read it), and a non-final
+// segment stops at the first chunk start s with s + MAX > N, whose cut the
+// arena can no longer decide; the next segment starts HBX_SEG_OVERLAP = MAX
+// bytes before this one's end, so that start lies inside it.  Every
+// candidate of a resumed chunk is >= MIN into the arena, where K1's digests
+// (window-local) are those of the whole file.
+template <bool SEG>
+__device__ __forceinline__ void k2_chain(
     const uint8_t* __restrict__ arena, const uint64_t* __restrict__ file_off,
     const uint64_t* __restrict__ file_len, const uint64_t* __restrict__ slice_base,
     const uint2* __restrict__ ssum,
     const uint64_t* __restrict__ cut_base, uint64_t* __restrict__ cut_ends,
-    uint32_t* __restrict__ cut_count, uint32_t* __restrict__ zero_word) {
+    uint32_t* __restrict__ cut_count, uint32_t* __restrict__ zero_word,
+    const uint64_t* __restrict__ carry_ptr, const uint64_t* __restrict__ seg_off,
+    const uint64_t* __restrict__ seg_final, uint64_t* __restrict__ first_start) {
   const uint32_t f = blockIdx.x;
   const uint32_t l = threadIdx.x;
   // K2r's chain counter (which follows on the same stream), zeroed here
@@ -450,7 +463,25 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k2_cut_chain(
   const uint64_t cb = cut_base[f];
   uint64_t s = 0;
   uint32_t k = 0;
-  while (s < N) {
+  bool final = true;
+  uint64_t so = 0;
+  uint64_t* carry = nullptr;
+  if constexpr (SEG) {
+    so = seg_off[f];
+    final = seg_final[f] != 0ull;
+    carry = reinterpret_cast<uint64_t*>(carry_ptr[f]);
+    // the previous segment's K2 precedes this one on the cut stream: its
+    // store is visible at the kernel boundary
+    const uint64_t ld = so ? *carry : 0ull;
+    // every lane loaded the same word; say so (readfirstlane), or the whole
+    // chain below is compiled as divergent code (guide T20)
+    const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ld >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ld);
+    // (a carry outside the arena can only come from a bug: emit nothing)
+    s = at >= so && at - so <= N ? at - so : N;
+    if (l == 0) first_start[f] = s;
+  }
+  while (s < N && (!SEG || final || s + kMaxBlock <= N)) {
     const uint64_t L = umin64(kMaxBlock, N - s);  // store.go:116-120
     uint64_t cut;
     if (L <= 2ull * kMinBlock) {  // store.go:129-130: no split candidate
@@ -531,6 +562,36 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k2_cut_chain(
     s = cut;
   }
   if (l == 0) cut_count[f] = k;
+  if constexpr (SEG) {
+    if (l == 0) *carry = so + s;
+  }
+}
+
+extern "C" __global__ __launch_bounds__(64) void hbx_k2_cut_chain(
+    const uint8_t* __restrict__ arena, const uint64_t* __restrict__ file_off,
+    const uint64_t* __restrict__ file_len, const uint64_t* __restrict__ slice_base,
+    const uint2* __restrict__ ssum,
+    const uint64_t* __restrict__ cut_base, uint64_t* __restrict__ cut_ends,
+    uint32_t* __restrict__ cut_count, uint32_t* __restrict__ zero_word) {
+  k2_chain<false>(arena, file_off, file_len, slice_base, ssum, cut_base, cut_ends, cut_count, zero_word, nullptr,
+                  nullptr, nullptr, nullptr);
+}
+
+// K2 over one segment per file (hbx_seg_submit_device): one wave per
+// file-segment.  carry_ptr[f] is the device address of file f's 8-byte carry
+// word, seg_off[f] the file offset of arena byte 0, seg_final[f] != 0 for the
+// file's last segment; first_start[f] receives the arena-relative start of
+// the segment's first chunk (for K2r).  cut_ends stay arena-relative.
+extern "C" __global__ __launch_bounds__(64) void hbx_k2s_cut_chain_seg(
+    const uint8_t* __restrict__ arena, const uint64_t* __restrict__ file_off,
+    const uint64_t* __restrict__ file_len, const uint64_t* __restrict__ slice_base,
+    const uint2* __restrict__ ssum,
+    const uint64_t* __restrict__ cut_base, uint64_t* __restrict__ cut_ends,
+    uint32_t* __restrict__ cut_count, uint32_t* __restrict__ zero_word,
+    const uint64_t* __restrict__ carry_ptr, const uint64_t* __restrict__ seg_off,
+    const uint64_t* __restrict__ seg_final, uint64_t* __restrict__ first_start) {
+  k2_chain<true>(arena, file_off, file_len, slice_base, ssum, cut_base, cut_ends, cut_count, zero_word, carry_ptr,
+                 seg_off, seg_final, first_start);
 }
 
 // -------------------------------------------------------------- MD5 -----
@@ -1007,21 +1068,25 @@ __device__ __forceinline__ uint32_t plan_bin(const OrderEntry& o, uint32_t budge
 // ------------------------------------------------------- K2r new chains --
 // One chain per chunk of a new batch, in any order, into the batch's array;
 // one order entry per chain into `fresh`; count in cnt[0] (zeroed before).
+// first_start (may be null: 0 for every file) = per file, where chunk 0 starts.
 constexpr uint32_t kPlanLanesPerFile = 16u;  // work items sharing one file's chunks
 
 extern "C" __global__ __launch_bounds__(256) void hbx_k2r_new_chains(
     uint32_t n_files, const uint8_t* __restrict__ arena, const uint64_t* __restrict__ file_off,
     const uint64_t* __restrict__ cut_base, const uint64_t* __restrict__ cut_ends,
     const uint32_t* __restrict__ cut_count, uint32_t* __restrict__ ids, Chain* __restrict__ run,
-    OrderEntry* __restrict__ fresh, uint32_t* __restrict__ cnt) {
+    OrderEntry* __restrict__ fresh, uint32_t* __restrict__ cnt, const uint64_t* __restrict__ first_start) {
   const uint32_t w = blockIdx.x * 256u + threadIdx.x;
   if (w >= n_files * kPlanLanesPerFile) return;
   const uint32_t f = w / kPlanLanesPerFile;
   const uint64_t cb = cut_base[f];
   const uint32_t k = cut_count[f];
   const uint64_t base = reinterpret_cast<uint64_t>(arena + file_off[f]);
+  // chunk 0 starts at the file's start, or (a segment, hbx_k2s_cut_chain_seg)
+  // where the file's previous segment stopped
+  const uint64_t s0 = first_start ? first_start[f] : 0ull;
   for (uint32_t i = w % kPlanLanesPerFile; i < k; i += kPlanLanesPerFile) {
-    const uint64_t start = i ? cut_ends[cb + i - 1] : 0ull;
+    const uint64_t start = i ? cut_ends[cb + i - 1] : s0;
     const uint64_t e = cut_ends[cb + i];
     Chain ch;
     ch.src = base + start;
@@ -1990,6 +2055,32 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k5_md5_raw(const uint8_t* _
   out[1] = h[1];
   out[2] = h[2];
   out[3] = h[3];
+}
+
+// The same MD5 for a message of at least one full block, 4-byte aligned and
+// followed by 128 readable bytes: block 0 from the message's own words, the
+// rest through md5_run, whose chain message BE32(0) || BE32(len') || c equals
+// the raw message from block 1 on for c = msg + 8, len' = n - 8 (and pads to
+// the same bit length).  Every lane runs the same chain (one address per
+// load: a broadcast); lane 0 stores.  Much faster than K5's byte-at-a-time
+// loop: the FileChainBlock id of a segmented file (16 + 48 bytes per chunk)
+// goes through it.
+extern "C" __global__ __launch_bounds__(64) void hbx_k5r_md5_run(const uint8_t* __restrict__ msg, uint32_t n,
+                                                                 uint32_t* __restrict__ out) {
+  uint32_t h[4];
+  md5_init(h);
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(msg);
+  uint32_t m[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) m[i] = w[i];
+  md5_compress(h, m);
+  md5_run<>(msg + 8, n - 8u, h, 1u, (n >> 6) - 1u, true);
+  if (threadIdx.x == 0) {
+    out[0] = h[0];
+    out[1] = h[1];
+    out[2] = h[2];
+    out[3] = h[3];
+  }
 }
 
 // ------------------------------------------------------------ K6 verify --

@@ -36,6 +36,8 @@ CONTENT_TYPE_FILE_DATA = 2  # store.go:193
 CONTENT_TYPE_FILE_CHAIN = 3  # store.go:189
 ARENA_ALIGN = 16
 ARENA_SLACK = 64
+SEG_OVERLAP = MAX_BLOCK_SIZE  # HBX_SEG_OVERLAP
+SEG_MIN_BYTES = 2 * MAX_BLOCK_SIZE  # HBX_SEG_MIN_BYTES
 
 BytesLike = Union[bytes, bytearray, memoryview, np.ndarray]
 
@@ -90,6 +92,37 @@ def _huge_host_buffer(nbytes: int) -> np.ndarray:
         except OSError:
             pass
     return np.frombuffer(m, np.uint8)  # the array keeps the mapping alive
+
+
+class SegmentedFile:
+    """An open segmented file (hbx_seg_open): the handle :meth:`Engine.seg_submit_device`
+    takes.  ``end`` is the file offset where the latest submitted segment
+    ends (0 before the first), ``final_sent`` whether the final one went in."""
+
+    def __init__(self, engine: "Engine", handle: int, file_len: int):
+        self._engine = engine
+        self._h = ctypes.c_void_p(handle)
+        self.file_len = int(file_len)
+        self.end = 0
+        self.final_sent = False
+
+    def next(self, segment_bytes: int):
+        """(offset, length) of the next segment to submit (hbx_seg_next)."""
+        return Engine.seg_next(self.file_len, segment_bytes, self.end)
+
+    def close(self):
+        """hbx_seg_close: refused (HbxError) while a segment is pending;
+        before the final segment it abandons the file."""
+        if self._h:
+            e = self._engine
+            e._check(e._L.hbx_seg_close(e._ctx, self._h), "hbx_seg_close")
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Engine:
@@ -246,6 +279,12 @@ class Engine:
         rc = self._L.hbx_wait(self._ctx)
         self.wait_s += time.perf_counter() - t  # time inside hbx_wait (bench diagnostics)
         self._check(rc, "hbx_wait")
+        if isinstance(item[0], str) and item[0] == "seg":
+            _, lens, caps, base, cuts, ids, sums, _keep = item
+            sv = np.ctypeslib.as_array(sums)[:len(lens)]
+            return [FileChunks(cuts[b:b + k], ids[b:b + k], int(t), bytes(c.tobytes()) if t else b"")
+                    for b, k, t, c in zip(base.astype(np.int64).tolist(), sv["n_chunks"].tolist(),
+                                          sv["content_type"].tolist(), sv["content_id"])]
         if isinstance(item[0], str):  # ("verify", ...)
             _, n, ids, ok, bad, keep = item
             return ids[:n], (ok[:n].astype(bool) if keep[1] is not None else None), int(bad.value)
@@ -664,11 +703,118 @@ class Engine:
         self._check(self._L.hbx_io_times(self._ctx, s, int(bool(reset))), "hbx_io_times")
         return np.array(list(s), np.float64)
 
-    def store_file(self, path: Union[str, os.PathLike]) -> FileChunks:
-        """storeFile(path) for a regular file on disk (store.go:84-199)."""
-        with open(path, "rb") as fh:
-            data = np.fromfile(fh, dtype=np.uint8)
-        return self.chunk_hash(data)
+    def store_file(self, path: Union[str, os.PathLike], segment_bytes: Optional[int] = None,
+                   io_threads: int = 16) -> FileChunks:
+        """storeFile(path) for a regular file on disk (store.go:84-199).  With
+        ``segment_bytes`` the file streams through the pipeline in segments of
+        that size (hbx_store_file_seg): host and device memory then depend on
+        the segment size only, so a file may be larger than device memory."""
+        if segment_bytes is None:
+            with open(path, "rb") as fh:
+                data = np.fromfile(fh, dtype=np.uint8)
+            return self.chunk_hash(data)
+        n = os.stat(path).st_size
+        cap = max_chunks(n)
+        cuts = np.zeros(cap, np.uint64)
+        ids = np.zeros((cap, 16), np.uint8)
+        s = _lib.FileSummary()
+        self._check(self._L.hbx_store_file_seg(self._ctx, os.fsencode(path), n, int(segment_bytes), int(io_threads),
+                                               _p(cuts), _p(ids), cap, ctypes.byref(s)), "hbx_store_file_seg")
+        k = int(s.n_chunks)
+        return FileChunks(cuts[:k], ids[:k], int(s.content_type), bytes(s.content_id) if k else b"")
+
+    # ---------------------------------------------------- segmented files --
+    @staticmethod
+    def seg_next(file_len: int, segment_bytes: int, prev_end: int = 0):
+        """hbx_seg_next: (offset, length) of the segment after the one that
+        ended at ``prev_end`` (0: the first).  Segments overlap by
+        SEG_OVERLAP bytes; the one with offset + length == file_len is final.
+        Raises ValueError for a bad segment size or when nothing is left."""
+        off, ln = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = _lib.load().hbx_seg_next(int(file_len), int(segment_bytes), int(prev_end), ctypes.byref(off),
+                                      ctypes.byref(ln))
+        if rc != 0:
+            raise ValueError(f"hbx_seg_next({file_len}, {segment_bytes}, {prev_end}): {_lib.ERRORS.get(rc, rc)}")
+        return int(off.value), int(ln.value)
+
+    def seg_open(self, file_len: int) -> SegmentedFile:
+        """Open a file of ``file_len`` bytes for segmented submission."""
+        h = ctypes.c_void_p()
+        self._check(self._L.hbx_seg_open(self._ctx, int(file_len), ctypes.byref(h)), "hbx_seg_open")
+        return SegmentedFile(self, h.value, file_len)
+
+    def seg_submit_device(self, files: Sequence[SegmentedFile], d_arena: int, arena_offs: Sequence[int],
+                          seg_lens: Sequence[int], seg_offs: Optional[Sequence[int]] = None):
+        """Enqueue one batch holding the next segment of each of ``files``
+        (distinct open files), resident at ``d_arena + arena_offs[i]``
+        (hbx_seg_submit_device).  ``seg_offs`` (optional) are the file offsets
+        the caller filled the arenas from; they are checked against what each
+        handle expects (ValueError).  :meth:`wait` returns one FileChunks per
+        segment: absolute cut ends, this segment's chunks, content type 0 for
+        a non-final segment and the whole file's type and id for the final."""
+        self._after_producer()
+        offs = np.ascontiguousarray(arena_offs, np.uint64)
+        lens = np.ascontiguousarray(seg_lens, np.uint64)
+        if not (len(files) == offs.size == lens.size):
+            raise ValueError("one arena offset and one length per file")
+        if seg_offs is not None:
+            for f, o in zip(files, seg_offs):
+                want = f.end - SEG_OVERLAP if f.end else 0
+                if int(o) != want:
+                    raise ValueError(f"segment offset {int(o)}: the file's next segment starts at {want}")
+        caps, base, cuts, ids, sums = self._alloc_out(lens)
+        hs = (ctypes.c_void_p * max(len(files), 1))(*[f._h for f in files])
+        self._check(self._L.hbx_seg_submit_device(self._ctx, len(files), hs, ctypes.c_void_p(int(d_arena)), _p(offs),
+                                                  _p(lens), _p(cuts), _p(ids), _p(base), _p(caps), sums),
+                    "hbx_seg_submit_device")
+        for f, ln in zip(files, lens.tolist()):
+            f.end = (f.end - SEG_OVERLAP if f.end else 0) + int(ln)
+            f.final_sent = f.end == f.file_len
+        self._pending.append(("seg", lens, caps, base, cuts, ids, sums, (offs, hs)))
+
+    def chunk_hash_segmented(self, data: BytesLike, segment_bytes: int, return_segments: bool = False):
+        """storeFile over one in-memory file, streamed through a ring of three
+        device arenas of ``segment_bytes`` in overlapping segments: the result
+        of :meth:`chunk_hash` for a file of any size.  With
+        ``return_segments`` also the number of chunks each segment completed."""
+        a = _u8(data)
+        n = int(a.size)
+        if self._pending:
+            raise HbxError("chunk_hash_segmented: batches are pending")
+        self.seg_next(n, segment_bytes, 0)  # a bad segment size raises before anything is allocated
+        arenas, parts = [], []
+        f = self.seg_open(n)
+        try:
+            for _ in range(3):
+                d = ctypes.c_void_p()
+                self._check(self._L.hbx_arena_alloc(self._ctx, min(int(segment_bytes), n) + 1, ctypes.byref(d)),
+                            "hbx_arena_alloc")
+                arenas.append(d)
+            k = 0
+            while not f.final_sent:
+                off, ln = f.next(segment_bytes)
+                if k >= 3:  # the arena's previous segment must be collected
+                    parts += self.wait()
+                if ln:
+                    self.memcpy_h2d_async(arenas[k % 3].value, a.ctypes.data + off, ln)
+                self.seg_submit_device([f], arenas[k % 3].value, [0], [ln], seg_offs=[off])
+                k += 1
+            while self._pending:
+                parts += self.wait()
+        finally:
+            while self._pending:  # (after a failure: nothing may stay in flight on the arenas)
+                try:
+                    self.wait()
+                except HbxError:
+                    self._pending.clear()
+            f.close()
+            for d in arenas:
+                self._L.hbx_arena_free(self._ctx, d)
+        last = parts[-1]
+        cuts = np.concatenate([p.cut_ends for p in parts]) if parts else np.zeros(0, np.uint64)
+        ids = np.concatenate([p.ids for p in parts]) if parts else np.zeros((0, 16), np.uint8)
+        res = FileChunks(cuts, ids, last.content_type, last.content_id if cuts.size else b"")
+        return (res, [p.n_chunks for p in parts]) if return_segments else res
 
     def stage_times(self) -> np.ndarray:
         """Device ms of the last collected batch: K1, K2, plan + first K3

@@ -181,6 +181,84 @@ int hbx_store_paths(hbx_ctx *ctx, uint64_t n_files, const char *const *paths,
                     const uint64_t *out_base, const uint64_t *caps, hbx_file_summary *summaries,
                     uint32_t io_threads, uint64_t batch_bytes);
 
+/* ---- Files larger than a batch: segments ------------------------------------
+ * storeFile (hashback/store.go:84-199) reads a file of any size through an
+ * 8 MiB window; the calls above need a whole file resident in one arena.
+ * These stream one file through the pipeline as a sequence of SEGMENTS that
+ * overlap by HBX_SEG_OVERLAP bytes.  store.go:111-166 decides each cut from
+ * file[s : s + min(MAX, N - s)] alone, so a segment's cut chain is exact for
+ * every chunk start s with s + MAX <= the segment's length (or up to the end
+ * of the file in the final segment); it stops at the first start beyond that,
+ * which lies strictly inside the overlap, and the next segment resumes there.
+ * That resume point (the file's CARRY, an absolute offset) goes from one
+ * segment's cut kernel to the next in device memory, so the segments of a
+ * file pipeline like independent batches: no host round trip, no drain, and
+ * hbx_wait stays FIFO.  The overlap is scanned twice (K1); no byte is hashed
+ * twice.  Results are those of the whole file in one piece. */
+#define HBX_SEG_OVERLAP HBX_MAX_BLOCK_SIZE          /* segment j+1 starts this far before segment j's end */
+#define HBX_SEG_MIN_BYTES (2u * HBX_MAX_BLOCK_SIZE) /* smallest non-final segment: the carried start is <=
+                                                       OVERLAP into it, so at least one chunk completes */
+typedef struct hbx_seg hbx_seg;
+
+/* The next segment of a file of file_len bytes cut into segments of seg_bytes
+ * (>= HBX_SEG_MIN_BYTES, a multiple of HBX_ARENA_ALIGN): *off = 0 for the
+ * first (prev_end == 0), else prev_end - HBX_SEG_OVERLAP, where prev_end is
+ * the previous segment's end (off + len); *len = min(seg_bytes, file_len -
+ * off).  The segment with off + len == file_len is the final one.
+ * HBX_ERR_ARG for a bad seg_bytes, or if prev_end > 0 and nothing is left.
+ * Pure host arithmetic, no context. */
+int hbx_seg_next(uint64_t file_len, uint64_t seg_bytes, uint64_t prev_end, uint64_t *off, uint64_t *len);
+/* Open a file of file_len bytes for segmented submission.  The handle owns
+ * the file's carry word (device memory) and the chunk IDs collected so far
+ * (host memory, 16 bytes per chunk: the final FileChainBlock's links). */
+int hbx_seg_open(hbx_ctx *ctx, uint64_t file_len, hbx_seg **out);
+/* Close a handle: HBX_ERR_STATE while one of its segments is pending.
+ * Closing before the final segment was submitted abandons the file. */
+int hbx_seg_close(hbx_ctx *ctx, hbx_seg *seg);
+/* Enqueue one batch of n >= 1 segments, segment i being the next one of the
+ * open file segs[i] (distinct files) at d_arena[arena_offs[i] .. +seg_lens[i]):
+ * otherwise as hbx_submit_device, completed by hbx_wait in FIFO order with
+ * every other batch.  Each segment must be what hbx_seg_next gives for its
+ * file (the handle tracks the previous end, so the offset is implied and only
+ * the length is passed): a non-final segment shorter than HBX_SEG_MIN_BYTES
+ * or not a multiple of HBX_ARENA_ALIGN, or one longer than the rest of the
+ * file, is HBX_ERR_ARG; a segment after the final one is HBX_ERR_STATE;
+ * caps[i] < hbx_max_chunks(seg_lens[i]) is HBX_ERR_CAPACITY; all before
+ * anything is enqueued.  At completion cut_ends are ABSOLUTE file offsets,
+ * summaries[i].n_chunks is the number of chunks this segment completed (a
+ * segment's first chunk starts at the previous segment's last cut end), and
+ * content_type is 0 for a non-final segment.  The final segment's summary
+ * carries the whole file's content_type and content_id (store.go:187-196):
+ * type 2 and the chunk's ID with one chunk in total, else type 3 and the ID
+ * of the FileChainBlock over all the file's chunk IDs, hashed on the device
+ * by that hbx_wait without draining the other batches (a file with more
+ * chunks than one block's BE32 length framing holds fails that wait with
+ * HBX_ERR_CAPACITY).  The "file too large" limits apply per segment. */
+int hbx_seg_submit_device(hbx_ctx *ctx, uint64_t n, hbx_seg *const *segs, const void *d_arena,
+                          const uint64_t *arena_offs, const uint64_t *seg_lens, uint64_t *cut_ends,
+                          uint8_t *ids, const uint64_t *out_base, const uint64_t *caps,
+                          hbx_file_summary *summaries);
+/* storeFile(path) for a file of any size: io_threads read each segment's
+ * byte range in parallel (ranged pread) into two pinned slots; each segment is
+ * copied into a ring of device arenas and submitted as above, so reading
+ * segment j+1 never waits for segment j's cuts.  file_len must be the file's
+ * size (stat); a short read fails the call with HBX_ERR_IO.  cut_ends / ids
+ * (cap entries; HBX_ERR_CAPACITY with summary->n_chunks set if the file has
+ * more chunks) and *summary receive the whole file's results, as
+ * hbx_chunk_hash_batch gives them for a file in memory.
+ * Memory bound: with S = min(seg_bytes, file_len) + 64 KiB, pinned host
+ * memory is 2 S and device memory is D S for the arena ring plus the
+ * pipeline's per-batch buffers for D + 2 batches of S bytes, D being the ring
+ * depth hbx_store_paths uses (2..64, from the MD5 slice, join lag and K3
+ * period: 10 at the defaults).  None of it depends on file_len.  What grows
+ * with the file is 24 bytes of pageable host memory per chunk (its ID and cut
+ * end), and 48 bytes per chunk of host and device memory for the final
+ * FileChainBlock message while its ID is hashed (about 11 MB per TiB).
+ * Synchronous; refused (HBX_ERR_STATE) while batches are pending. */
+int hbx_store_file_seg(hbx_ctx *ctx, const char *path, uint64_t file_len, uint64_t seg_bytes,
+                       uint32_t io_threads, uint64_t *cut_ends, uint8_t *ids, uint64_t cap,
+                       hbx_file_summary *summary);
+
 /* Host seconds hbx_store_paths spent, cumulative per context: [0] reading
  * files into pinned memory, [1] waiting for batches to be collected (a device
  * arena's reuse, and the drain at the end of the call), [2] waiting for a
