@@ -37,10 +37,12 @@ EXPORTS = [
     "hbx_input_fence", "hbx_set_k3_probe", "hbx_store_paths_status", "hbx_plan_pipeline", "hbx_apply_plan",
     "hbx_host_call_max",
     "hbx_seg_next", "hbx_seg_open", "hbx_seg_close", "hbx_seg_submit_device", "hbx_store_file_seg",
+    "hbx_idset_slots", "hbx_idset_create", "hbx_idset_destroy", "hbx_idset_insert", "hbx_idset_contains",
+    "hbx_idset_stats", "hbx_idset_export", "hbx_idset_truncate", "hbx_submit_device_dd", "hbx_store_paths_dd",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
-               "hbx_directory_block_size", "hbx_deflate_bound", "hbx_deflate_file_bound")
+               "hbx_directory_block_size", "hbx_deflate_bound", "hbx_deflate_file_bound", "hbx_idset_slots")
 
 
 class FileEntry(ctypes.Structure):
@@ -194,6 +196,17 @@ def load() -> ctypes.CDLL:
     L.hbx_seg_close.argtypes = [P, P]
     L.hbx_seg_submit_device.argtypes = [P, U64, P, P, P, P, P, P, P, P, P]
     L.hbx_store_file_seg.argtypes = [P, ctypes.c_char_p, U64, U64, ctypes.c_uint32, P, P, U64, P]
+    L.hbx_idset_slots.argtypes = [U64]
+    L.hbx_idset_slots.restype = U64
+    L.hbx_idset_create.argtypes = [P, U64, ctypes.POINTER(P)]
+    L.hbx_idset_destroy.argtypes = [P, P]
+    L.hbx_idset_insert.argtypes = [P, P, U64, P, P]
+    L.hbx_idset_contains.argtypes = [P, P, U64, P, P]
+    L.hbx_idset_stats.argtypes = [P, P, PU64, PU64, PU64, PU64]
+    L.hbx_idset_export.argtypes = [P, P, P, U64, PU64]
+    L.hbx_idset_truncate.argtypes = [P, P, U64]
+    L.hbx_submit_device_dd.argtypes = L.hbx_submit_device.argtypes + [P, P]
+    L.hbx_store_paths_dd.argtypes = L.hbx_store_paths_status.argtypes + [P, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

@@ -38,6 +38,7 @@
 #include "hbx_deflate.hip"
 #include "hbx_inflate.hip"
 #include "hbx_inflate_split.hip"
+#include "hbx_dedup.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 
@@ -112,15 +113,20 @@ struct TimedLaunch {
 // pinned host block (h_res), so one copy moves them all.
 struct ResLayout {
   size_t counts = 0, cuts = 0, ids = 0, cid = 0, ctype = 0, total = 0;
+  size_t fresh = 0;  // K9 flags, one byte per result slot: only for a batch submitted with an ID set
 };
 inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-ResLayout res_layout(uint64_t n_files, uint64_t total_cap) {
+ResLayout res_layout(uint64_t n_files, uint64_t total_cap, bool dedup = false) {
   ResLayout r;
   r.cuts = al256(n_files * 4);
   r.ids = r.cuts + al256(total_cap * 8);
   r.cid = r.ids + al256(total_cap * 16);
   r.ctype = r.cid + al256(n_files * 16);
   r.total = r.ctype + al256(n_files * 4);
+  if (dedup) {  // behind everything else: the layout and the copy of a batch without a set do not change
+    r.fresh = r.total;
+    r.total += al256(total_cap);
+  }
   return r;
 }
 
@@ -140,6 +146,23 @@ struct hbx_seg {
   std::vector<uint8_t> ids;   // the file's chunk ids collected so far (the chain block's links)
   bool keep_cuts = false;     // hbx_store_file_seg: collect the cut ends here too
   std::vector<uint64_t> cuts;
+};
+
+// A set of block IDs in device memory (hbx_idset_create; layout and kernels:
+// hbx_dedup.hip).  Every kernel that touches it runs on the context's result
+// stream, so marks, lookups and rebuilds are ordered by that stream alone.
+struct hbx_idset {
+  uint64_t capacity = 0, slots = 0;
+  DevBuf d_keys, d_slots, d_ctl;
+  DevBuf d_in, d_flag, d_scratch;  // the direct calls' staging: IDs, flags, scratch slot table
+  uint32_t inflight = 0;           // pending batches submitted with it
+  hbxd::Set view() const {
+    return hbxd::Set{d_keys.as<uint4>(), d_slots.as<uint32_t>(), d_ctl.as<uint32_t>(), (uint32_t)capacity,
+                     (uint32_t)(slots - 1)};
+  }
+  void release() {
+    for (DevBuf* d : {&d_keys, &d_slots, &d_ctl, &d_in, &d_flag, &d_scratch}) d->release();
+  }
 };
 
 namespace {
@@ -180,6 +203,12 @@ struct Batch {
   std::vector<hbx_seg*> segs;
   std::vector<uint64_t> seg_off;
   std::vector<uint8_t> seg_final;
+  // submitted with an ID set (hbx_submit_device_dd): K9 marks its result slots
+  // when it is finalized, dd_seq-th of the context's marks; the flags go to
+  // fresh_out[out_base[f] + q] at the collect
+  hbx_idset* set = nullptr;
+  uint8_t* fresh_out = nullptr;
+  uint64_t dd_seq = 0;
   // K1 start | K1 end | K2r end | plan+K3 end (first) | results ready | K2 end (lean marks)
   hipEvent_t ev[6] = {};
   void release() {
@@ -372,6 +401,13 @@ struct hbx_ctx {
   // memory, which would wait for the device), the final chain block's
   // message and the stream its block id is computed on (created by the first
   // hbx_seg_open; beside, never inside, the pipeline's four streams)
+  // hbx_idset_*: the context's ID sets; the scratch slot table of the pipeline's
+  // marks (one at a time: they all run on the result stream); marks are
+  // numbered at submit (dd_submitted) and must be enqueued in that order
+  // (dd_marked, finalize_batch)
+  std::vector<hbx_idset*> idsets;
+  DevBuf d_dscratch;
+  uint64_t dd_submitted = 0, dd_marked = 0;
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -539,6 +575,9 @@ Batch* acquire_batch(hbx_ctx* c) {
   b->segs.clear();
   b->seg_off.clear();
   b->seg_final.clear();
+  b->set = nullptr;
+  b->fresh_out = nullptr;
+  b->dd_seq = 0;
   return b;
 }
 
@@ -616,6 +655,17 @@ int finalize_batch(hbx_ctx* c, Batch* b) {
                          reinterpret_cast<int32_t*>(b->res(b->rl.ctype)), c->k4_window);
     }
     HBX_TRY(c, hipGetLastError());
+    if (b->set) {
+      // K9: one mark over the batch's result slots.  "First in submit order"
+      // holds because every mark is enqueued here, on the one result stream,
+      // in the order of the submits (md5_launch holds a batch back until the
+      // older batches with a set are marked)
+      if (b->dd_seq != c->dd_marked) return c->fail(HBX_ERR_STATE, "ID set marks out of submit order (internal)");
+      c->dd_marked++;
+      const hbxd::Ids in{reinterpret_cast<const uint4*>(b->res(b->rl.ids)), d_cb, b->count_d(), (uint32_t)b->caps,
+                         (uint32_t)n};
+      HBX_TRY(c, hbxd::mark(s, b->set->view(), in, c->d_dscratch.as<uint32_t>(), b->res(b->rl.fresh)));
+    }
     g_slow.lap(0, lap);
     // one copy for every result (5 copies before: each a dispatch on this stream)
     if (c->d2h_kernel && b->rl.total % 16 == 0) {
@@ -851,10 +901,20 @@ int md5_launch(hbx_ctx* c, const std::vector<Batch*>& nbs, uint32_t budget) {
       nb->ev3 = true;
     }
   bool forked = false;
+  bool dd_older = false;  // an older batch with an ID set is not finalized yet: its mark goes first
   for (Batch* b : c->pending) {
-    if (b->finalized || !b->joined) continue;
+    if (b->finalized) continue;
+    if (!b->joined) {
+      dd_older = dd_older || b->set;
+      continue;
+    }
     b->done++;
-    if (budget == kBudgetAll || b->done >= b->need) {
+    const bool hashed = budget == kBudgetAll || b->done >= b->need;
+    if (b->set && (dd_older || !hashed)) {  // (held back: finalized by the launch that finalizes the older ones)
+      dd_older = true;
+      continue;
+    }
+    if (hashed) {
       if (!forked && c->rstream != s) {  // the result stream picks up after this K3
         HBX_TRY(c, hipStreamWaitEvent(c->rstream, c->order_free[L % kDoneRing], 0));
         forked = true;
@@ -1021,27 +1081,27 @@ inline uint64_t scan_iters(uint64_t N) {  // K1 iterations of a file (0: no spli
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                        const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
-                       const uint64_t* seg_offs);
+                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh);
 }  // namespace
 // hbx_reserve with the context's lock already held (defined beside it, inside
 // the C-ABI block; not exported)
 extern "C" __attribute__((visibility("hidden"))) int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files,
-                                                                    uint64_t bytes);
+                                                                    uint64_t bytes, bool dedup = false);
 namespace {
 int submit_batch(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                  const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                  const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs = nullptr,
-                 const uint64_t* seg_offs = nullptr) {
+                 const uint64_t* seg_offs = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = submit_batch_timed(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, budget, segs,
-                                    seg_offs);
+                                    seg_offs, set, fresh);
   c->max_submit_ms = std::max(c->max_submit_ms, ms_since(t0));
   return rc;
 }
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                        const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
-                       const uint64_t* seg_offs) {
+                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh) {
   g_slow.mark(0);
   g_slow.clear();
   if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
@@ -1087,6 +1147,10 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
     }
   }
   b->caps = tcaps;
+  if (set && tcaps > hbxd::kMaxMark) {
+    c->pool.push_back(b);
+    return c->fail(HBX_ERR_ARG, "too many chunks in one batch for an ID set");
+  }
   // launches this batch's chains need: a chunk is <= min(longest file, MAX)
   // bytes, i.e. <= nfull full message blocks, and each launch advances it by
   // slice_cnt(remaining, budget) blocks (the part short of a slice first, then
@@ -1102,7 +1166,7 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
   g_slow.mark(1);
   if (n) {  // every allocation first: the batch is not in the FIFO yet
     int rc = HBX_OK;
-    b->rl = res_layout(n, tcaps);
+    b->rl = res_layout(n, tcaps, set != nullptr);
     for (hipError_t e : {b->h_meta.ensure(meta_bytes), b->d_meta.ensure(meta_bytes), b->d_res.ensure(b->rl.total),
                          b->d_run.ensure(tcaps * sizeof(Chain)),
                          b->d_fresh.ensure(tcaps * sizeof(OrderEntry)), b->d_fcnt.ensure(256),
@@ -1110,7 +1174,14 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
       if (e != hipSuccess && !rc) rc = c->hip(e, "batch buffers");
     if (!rc) rc = ensure_shared(c, c->d_ssum[slot], (slices + 1) * sizeof(uint2));  // +1: dummy slot
     if (!rc) rc = ensure_plan_buffers(c, tcaps);
+    if (!rc && set) rc = ensure_shared(c, c->d_dscratch, hbxd::table_slots(tcaps) * sizeof(uint32_t));
     if (rc) return submit_abort(c, b, rc, false);
+    if (set) {  // (a batch without files has no chunk to mark)
+      b->set = set;
+      b->fresh_out = fresh;
+      b->dd_seq = c->dd_submitted++;
+      set->inflight++;
+    }
   }
   c->pending.push_back(b);
   g_slow.mark(2);
@@ -1486,7 +1557,9 @@ int collect_batch(hbx_ctx* c, Batch* b) {
     }
     if (b->cut_ends) std::memcpy(b->cut_ends + b->out_base[f], cuts + ib, k * 8);
     if (b->ids) std::memcpy(b->ids + 16 * b->out_base[f], hid + 16 * ib, k * 16);
+    if (b->set && b->fresh_out) std::memcpy(b->fresh_out + b->out_base[f], hr + rl.fresh + ib, k);
   }
+  if (b->set) b->set->inflight--;
   float ms = 0.f;
   // stage boundaries: K1 start | K1 end | K2 end | plan+K3 end | results
   // ready (K2's end is ev[5] where lean marks left ev[2] unrecorded)
@@ -1763,6 +1836,11 @@ void hbx_ctx_destroy(hbx_ctx* c) {
     (void)hipStreamSynchronize(c->sstream);
     (void)hipStreamDestroy(c->sstream);
   }
+  for (hbx_idset* t : c->idsets) {
+    t->release();
+    delete t;
+  }
+  c->d_dscratch.release();
   for (hbx_seg* h : c->segs_open) delete h;
   for (DevBuf& d : c->seg_words) d.release();
   c->d_segmsg.release();
@@ -1992,7 +2070,7 @@ int hbx_reserve(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes) {
   return reserve_locked(c, batches, files, bytes);
 }
 
-int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes) {
+int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes, bool dedup) {
   if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
   HBX_TRY(c, hipSetDevice(c->device));
   const uint64_t caps = bytes / HBX_MIN_BLOCK_SIZE + files;  // >= sum of max_chunks over the files
@@ -2007,13 +2085,14 @@ int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes)
     if (!rc) rc = ensure_shared(c, c->d_octl[t], 256);
     if (!rc) rc = ensure_shared(c, c->d_q[t], (((uint64_t)batches * caps + 64) / 64 + 2) * 8 * 8);
   }
+  if (!rc && dedup) rc = ensure_shared(c, c->d_dscratch, hbxd::table_slots(caps) * sizeof(uint32_t));
   if (rc) return rc;
   std::vector<Batch*> ready;
   while (ready.size() < batches) {
     Batch* b = acquire_batch(c);  // pooled first, then new
     if (!b) break;
     ready.push_back(b);
-    const size_t rbytes = res_layout(files, caps).total;
+    const size_t rbytes = res_layout(files, caps, dedup).total;
     for (auto r : {b->h_meta.ensure(meta_bytes), b->d_meta.ensure(meta_bytes), b->d_res.ensure(rbytes),
                    b->d_run.ensure(caps * sizeof(Chain)), b->d_fresh.ensure(caps * sizeof(OrderEntry)),
                    b->d_fcnt.ensure(256), b->h_res.ensure(rbytes)})
@@ -2057,12 +2136,21 @@ int hbx_chunk_hash_device(hbx_ctx* c, const void* d_arena, uint64_t n, const uin
 int hbx_submit_device(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                       const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids,
                       const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums) {
+  return hbx_submit_device_dd(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, nullptr, nullptr);
+}
+
+int hbx_submit_device_dd(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs, const uint64_t* lens,
+                         uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
+                         hbx_file_summary* sums, hbx_idset* set, uint8_t* fresh) {
   if (!c) return HBX_ERR_ARG;
   if (n && (!d_arena || !offs || !lens || !out_base || !caps)) return HBX_ERR_ARG;
+  if (set && !fresh) return HBX_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
+  if (set && std::find(c->idsets.begin(), c->idsets.end(), set) == c->idsets.end())
+    return c->fail(HBX_ERR_ARG, "not an ID set of this context");
   HBX_TRY(c, hipSetDevice(c->device));
   return submit_batch(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums,
-                      c->md5_slice ? c->md5_slice : kBudgetAll);
+                      c->md5_slice ? c->md5_slice : kBudgetAll, nullptr, nullptr, set, set ? fresh : nullptr);
 }
 
 int hbx_wait(hbx_ctx* c) {
@@ -2076,6 +2164,167 @@ int hbx_pending(hbx_ctx* c) {
   if (!c) return HBX_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
   return (int)c->pending.size();
+}
+
+// ---- K9: the set of block IDs (DESIGN.md §5 "K9", hbx_dedup.hip) ----------
+namespace {
+constexpr uint64_t kIdsetCallChunk = 1ull << 22;  // IDs per mark of a direct call: 64 MiB of staging at most
+
+// count and dropped as the device holds them (waits for the result stream).
+int idset_count(hbx_ctx* c, hbx_idset* t, uint64_t* count, uint64_t* dropped) {
+  uint32_t ctl[4] = {0, 0, 0, 0};
+  HBX_TRY(c, hipMemcpyAsync(ctl, t->d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, c->rstream));
+  HBX_TRY(c, hipStreamSynchronize(c->rstream));
+  if (count) *count = std::min<uint64_t>(ctl[0], t->capacity);
+  if (dropped) *dropped = (uint64_t)ctl[2] | ((uint64_t)ctl[3] << 32);
+  return HBX_OK;
+}
+
+// Keep the first m keys: count = m, the slot table cleared and rebuilt from them.
+int idset_truncate(hbx_ctx* c, hbx_idset* t, uint64_t m) {
+  uint64_t count = 0;
+  if (int rc = idset_count(c, t, &count, nullptr)) return rc;
+  if (m > count) return c->fail(HBX_ERR_ARG, "hbx_idset_truncate: the set holds fewer IDs");
+  if (m == count) return HBX_OK;
+  hipStream_t s = c->rstream;
+  const uint32_t m32 = (uint32_t)m;
+  HBX_TRY(c, hipMemcpyAsync(t->d_ctl.p, &m32, 4, hipMemcpyHostToDevice, s));
+  HBX_TRY(c, hipMemsetAsync(t->d_slots.p, 0, t->slots * sizeof(uint32_t), s));
+  if (m32) {
+    hipLaunchKernelGGL(hbx_k9_rebuild, dim3((m32 + hbxd::kThreads - 1) / hbxd::kThreads), dim3(hbxd::kThreads), 0, s,
+                       t->view(), m32);
+    HBX_TRY(c, hipGetLastError());
+  }
+  HBX_TRY(c, hipStreamSynchronize(s));  // (m32 is read by the copy above)
+  return HBX_OK;
+}
+
+// The checks every direct call shares; the context's lock is held.
+int idset_direct(hbx_ctx* c, hbx_idset* t) {
+  if (std::find(c->idsets.begin(), c->idsets.end(), t) == c->idsets.end())
+    return c->fail(HBX_ERR_ARG, "not an ID set of this context");
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  return c->hip(hipSetDevice(c->device), "hipSetDevice");
+}
+}  // namespace
+
+uint64_t hbx_idset_slots(uint64_t capacity) { return hbxd::table_slots(capacity); }
+
+int hbx_idset_create(hbx_ctx* c, uint64_t capacity, hbx_idset** out) {
+  if (!c || !out) return HBX_ERR_ARG;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(c->mu);
+  const uint64_t S = hbxd::table_slots(capacity);
+  if (capacity == 0 || S == 0) return c->fail(HBX_ERR_ARG, "hbx_idset_create: capacity must be 1..2^31");
+  HBX_TRY(c, hipSetDevice(c->device));
+  hbx_idset* t = new hbx_idset();
+  t->capacity = capacity;
+  t->slots = S;
+  int rc = HBX_OK;
+  for (hipError_t e : {t->d_keys.ensure(capacity * 16), t->d_slots.ensure(S * sizeof(uint32_t)), t->d_ctl.ensure(256)})
+    if (e != hipSuccess && !rc) rc = c->hip(e, "hbx_idset_create");
+  if (!rc) rc = c->hip(hipMemsetAsync(t->d_slots.p, 0, S * sizeof(uint32_t), c->rstream), "hbx_idset_create");
+  if (!rc) rc = c->hip(hipMemsetAsync(t->d_ctl.p, 0, 256, c->rstream), "hbx_idset_create");
+  if (!rc) rc = c->hip(hipStreamSynchronize(c->rstream), "hbx_idset_create");
+  if (rc) {
+    (void)hipGetLastError();
+    t->release();
+    delete t;
+    return rc;
+  }
+  c->idsets.push_back(t);
+  *out = t;
+  return HBX_OK;
+}
+
+int hbx_idset_destroy(hbx_ctx* c, hbx_idset* t) {
+  if (!c || !t) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  auto it = std::find(c->idsets.begin(), c->idsets.end(), t);
+  if (it == c->idsets.end()) return c->fail(HBX_ERR_ARG, "not an ID set of this context");
+  // (a broken context never collects: its batches are parked until destroy)
+  if (t->inflight && !c->broken) return c->fail(HBX_ERR_STATE, "pending batches still use the ID set");
+  HBX_TRY(c, hipSetDevice(c->device));
+  HBX_TRY(c, hipStreamSynchronize(c->rstream));
+  c->idsets.erase(it);
+  t->release();
+  delete t;
+  return HBX_OK;
+}
+
+int hbx_idset_insert(hbx_ctx* c, hbx_idset* t, uint64_t n, const uint8_t* ids, uint8_t* fresh) {
+  if (!c || !t || (n && !ids)) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (int rc = idset_direct(c, t)) return rc;
+  hipStream_t s = c->rstream;
+  // one mark per chunk of the list, in order: a later chunk finds what an
+  // earlier one inserted
+  for (uint64_t at = 0; at < n; at += kIdsetCallChunk) {
+    const uint64_t k = std::min(kIdsetCallChunk, n - at);
+    HBX_TRY(c, t->d_in.ensure(k * 16));
+    HBX_TRY(c, t->d_flag.ensure(k));
+    HBX_TRY(c, t->d_scratch.ensure(hbxd::table_slots(k) * sizeof(uint32_t)));
+    HBX_TRY(c, hipMemcpyAsync(t->d_in.p, ids + 16 * at, k * 16, hipMemcpyHostToDevice, s));
+    const hbxd::Ids in{t->d_in.as<uint4>(), nullptr, nullptr, (uint32_t)k, 0u};
+    HBX_TRY(c, hbxd::mark(s, t->view(), in, t->d_scratch.as<uint32_t>(), t->d_flag.as<uint8_t>()));
+    if (fresh) HBX_TRY(c, hipMemcpyAsync(fresh + at, t->d_flag.p, k, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+  }
+  return HBX_OK;
+}
+
+int hbx_idset_contains(hbx_ctx* c, hbx_idset* t, uint64_t n, const uint8_t* ids, uint8_t* found) {
+  if (!c || !t || (n && (!ids || !found))) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (int rc = idset_direct(c, t)) return rc;
+  hipStream_t s = c->rstream;
+  for (uint64_t at = 0; at < n; at += kIdsetCallChunk) {
+    const uint64_t k = std::min(kIdsetCallChunk, n - at);
+    HBX_TRY(c, t->d_in.ensure(k * 16));
+    HBX_TRY(c, t->d_flag.ensure(k));
+    HBX_TRY(c, hipMemcpyAsync(t->d_in.p, ids + 16 * at, k * 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(hbx_k9_contains, dim3((uint32_t)((k + hbxd::kThreads - 1) / hbxd::kThreads)),
+                       dim3(hbxd::kThreads), 0, s, t->view(), static_cast<const uint4*>(t->d_in.as<uint4>()),
+                       (uint32_t)k, t->d_flag.as<uint8_t>());
+    HBX_TRY(c, hipGetLastError());
+    HBX_TRY(c, hipMemcpyAsync(found + at, t->d_flag.p, k, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+  }
+  return HBX_OK;
+}
+
+int hbx_idset_stats(hbx_ctx* c, hbx_idset* t, uint64_t* count, uint64_t* capacity, uint64_t* slots,
+                    uint64_t* dropped) {
+  if (!c || !t) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (int rc = idset_direct(c, t)) return rc;
+  if (capacity) *capacity = t->capacity;
+  if (slots) *slots = t->slots;
+  return idset_count(c, t, count, dropped);
+}
+
+int hbx_idset_export(hbx_ctx* c, hbx_idset* t, uint8_t* ids, uint64_t cap, uint64_t* n) {
+  if (!c || !t || !n) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (int rc = idset_direct(c, t)) return rc;
+  uint64_t count = 0;
+  if (int rc = idset_count(c, t, &count, nullptr)) return rc;
+  *n = count;
+  if (count > cap) return c->fail(HBX_ERR_CAPACITY, "hbx_idset_export: the set holds " + std::to_string(count) + " IDs");
+  if (count && !ids) return c->fail(HBX_ERR_ARG, "hbx_idset_export: null output");
+  if (count) {
+    HBX_TRY(c, hipMemcpyAsync(ids, t->d_keys.p, count * 16, hipMemcpyDeviceToHost, c->rstream));
+    HBX_TRY(c, hipStreamSynchronize(c->rstream));
+  }
+  return HBX_OK;
+}
+
+int hbx_idset_truncate(hbx_ctx* c, hbx_idset* t, uint64_t count) {
+  if (!c || !t) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (int rc = idset_direct(c, t)) return rc;
+  return idset_truncate(c, t, count);
 }
 
 // ---- files larger than a batch: segments (DESIGN.md "Segmented files") ----
@@ -2445,7 +2694,11 @@ struct ZOut {
   uint64_t* zlen = nullptr;
   hbx_batch_ready_fn ready = nullptr;  // called once a batch's results are all written
   void* user = nullptr;
+  // hbx_store_paths_dd: the K9 flags (parallel to cut_ends); a chunk that is
+  // not fresh is not compressed, not copied back and not placed (zlen 0)
+  const uint8_t* fresh = nullptr;
 };
+constexpr uint64_t kNoStream = ~0ull;  // ZPend::dst of a chunk without a stream
 // A collected batch whose device arena still holds its files.
 struct ZJob {
   uint64_t first = 0, count = 0;
@@ -2471,7 +2724,7 @@ struct ZPend {
 };
 
 int z_start(hbx_ctx* c, ZPend& zp, const uint64_t* cut_ends, const uint64_t* out_base,
-            const hbx_file_summary* sums) {
+            const hbx_file_summary* sums, const uint8_t* fresh) {
   auto& Z = c->zs[zp.stage];
   std::vector<hbxz::ZBlock> zb;
   uint64_t d = 0, nseg = 0;
@@ -2481,6 +2734,11 @@ int z_start(hbx_ctx* c, ZPend& zp, const uint64_t* cut_ends, const uint64_t* out
     for (uint32_t q = 0; q < sums[f].n_chunks; q++) {
       const uint64_t e = cut_ends[out_base[f] + q];
       const uint64_t len = e - start, ns = (len + hbxz::kSeg - 1) / hbxz::kSeg;
+      if (fresh && !fresh[out_base[f] + q]) {  // seen before: the caller sends nothing for it
+        zp.dst.push_back(kNoStream);
+        start = e;
+        continue;
+      }
       zb.push_back(hbxz::ZBlock{reinterpret_cast<uint64_t>(zp.job.arena + zp.job.offs[i] + start), d, len,
                                 (uint32_t)nseg, (uint32_t)ns});
       zp.dst.push_back(d);
@@ -2537,7 +2795,9 @@ int z_finish(const hbx_ctx* c, ZPend& zp, const uint64_t* out_base, const hbx_fi
   const uint64_t nc = zp.dst.size();
   if (nc) {
     const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = hipEventSynchronize(Z.done);
+    // (a batch without a fresh chunk started no job: nothing to wait for)
+    const bool started = std::count(zp.dst.begin(), zp.dst.end(), kNoStream) != (int64_t)nc;
+    const hipError_t e = started ? hipEventSynchronize(Z.done) : hipSuccess;
     if (e != hipSuccess) {
       zp.err = std::string("hipEventSynchronize(compression stage): ") + hipGetErrorString(e);
       return HBX_ERR_HIP;
@@ -2547,23 +2807,26 @@ int z_finish(const hbx_ctx* c, ZPend& zp, const uint64_t* out_base, const hbx_fi
     const uint64_t* ol = Z.lens.as<uint64_t>();
     // placement (serial, cheap), then the copies out of the pinned stage on
     // `threads` threads (one thread copies a few GB/s)
-    std::vector<uint64_t> to(nc);
-    uint64_t k = 0;
+    // (ol and the stage hold the compressed chunks only, in order: zi)
+    std::vector<uint64_t> to(nc), zl(nc);
+    uint64_t k = 0, zi = 0;
     for (uint64_t i = 0; i < zp.job.count; i++) {
       const uint64_t f = zp.job.first + i;
       uint64_t run = z.zbase[f];
       for (uint32_t q = 0; q < sums[f].n_chunks; q++, k++) {
+        zl[k] = zp.dst[k] == kNoStream ? 0 : ol[zi++];
         to[k] = run;
         z.zoff[out_base[f] + q] = run;
-        z.zlen[out_base[f] + q] = ol[k];
-        run += ol[k];
+        z.zlen[out_base[f] + q] = zl[k];
+        run += zl[k];
       }
     }
     const uint32_t nt = std::max<uint32_t>(1u, std::min<uint32_t>(threads, 64u));
     std::vector<std::thread> pool;
     for (uint32_t t = 0; t < nt; t++)
       pool.emplace_back([&, t] {
-        for (uint64_t i = t; i < nc; i += nt) std::memcpy(z.zout + to[i], h + zp.dst[i], ol[i]);
+        for (uint64_t i = t; i < nc; i += nt)
+          if (zl[i]) std::memcpy(z.zout + to[i], h + zp.dst[i], zl[i]);
       });
     for (auto& th : pool) th.join();
   }
@@ -2574,7 +2837,7 @@ int z_finish(const hbx_ctx* c, ZPend& zp, const uint64_t* out_base, const hbx_fi
 int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
                      uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
                      hbx_file_summary* sums, uint32_t io_threads, uint64_t batch_bytes, const ZOut& z,
-                     int32_t* status = nullptr);
+                     int32_t* status = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr);
 }  // namespace
 
 int hbx_store_paths(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
@@ -2593,15 +2856,29 @@ int hbx_store_paths_status(hbx_ctx* c, uint64_t n, const char* const* paths, con
                            hbx_file_summary* sums, int32_t* status, uint32_t io_threads, uint64_t batch_bytes,
                            uint8_t* zout, const uint64_t* zbase, uint64_t* zoff, uint64_t* zlen,
                            hbx_batch_ready_fn ready, void* user) {
+  if (c && n && !status) return HBX_ERR_ARG;
+  return hbx_store_paths_dd(c, n, paths, lens, cut_ends, ids, out_base, caps, sums, status, io_threads, batch_bytes,
+                            zout, zbase, zoff, zlen, ready, user, nullptr, nullptr);
+}
+
+int hbx_store_paths_dd(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens, uint64_t* cut_ends,
+                       uint8_t* ids, const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums,
+                       int32_t* status, uint32_t io_threads, uint64_t batch_bytes, uint8_t* zout,
+                       const uint64_t* zbase, uint64_t* zoff, uint64_t* zlen, hbx_batch_ready_fn ready, void* user,
+                       hbx_idset* set, uint8_t* fresh) {
   if (!c) return HBX_ERR_ARG;
+  if (set && !fresh) return HBX_ERR_ARG;
   const bool z = zout || zbase || zoff || zlen;
-  if (n && (!paths || !lens || !out_base || !caps || !status)) return HBX_ERR_ARG;
+  if (n && (!paths || !lens || !out_base || !caps)) return HBX_ERR_ARG;
   if (n && z && (!sums || !zout || !zbase || !zoff || !zlen)) return HBX_ERR_ARG;
   if (!z && ready) return HBX_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
-  for (uint64_t i = 0; i < n; i++) status[i] = 0;
+  if (set && std::find(c->idsets.begin(), c->idsets.end(), set) == c->idsets.end())
+    return c->fail(HBX_ERR_ARG, "not an ID set of this context");
+  for (uint64_t i = 0; status && i < n; i++) status[i] = 0;
   return store_paths_impl(c, n, paths, lens, cut_ends, ids, out_base, caps, sums, io_threads, batch_bytes,
-                          z ? ZOut{zout, zbase, zoff, zlen, ready, user} : ZOut{}, status);
+                          z ? ZOut{zout, zbase, zoff, zlen, ready, user, set ? fresh : nullptr} : ZOut{}, status,
+                          set, set ? fresh : nullptr);
 }
 
 uint64_t hbx_deflate_file_bound(uint64_t len) {
@@ -2647,10 +2924,17 @@ size_t ring_depth(const hbx_ctx* c, uint32_t budget) {
 int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
                      uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
                      hbx_file_summary* sums, uint32_t io_threads, uint64_t batch_bytes, const ZOut& z,
-                     int32_t* status) {
+                     int32_t* status, hbx_idset* set, uint8_t* fresh) {
   if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
   HBX_TRY(c, hipSetDevice(c->device));
-  if (batch_bytes < (64ull << 20)) batch_bytes = 64ull << 20;
+  // with an ID set the batch size is the caller's down to 1 MiB (the flags do
+  // not depend on how the files fall into batches, and tests check that with
+  // small files); without one it is at least 64 MiB, as ever
+  const uint64_t batch_min = set ? 1ull << 20 : 64ull << 20;
+  if (batch_bytes < batch_min) batch_bytes = batch_min;
+  uint64_t set_count0 = 0;  // a failed call puts the set back to this
+  if (set)
+    if (int r0 = idset_count(c, set, &set_count0, nullptr)) return r0;
   for (hipEvent_t& e : c->h2d_done)
     if (!e) HBX_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   // Pipeline: files of batch k are read (io_threads) into pinned slot k % 2
@@ -2701,7 +2985,7 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
   // pooled batch that met a larger batch later reallocated its pinned meta and
   // result buffers inside that submit (19-28 ms per submit of config 5,
   // HBX_TRACE_SLOW_SUBMIT "buffers", profiles/r06e)
-  if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, most_files, biggest)) return r0;
+  if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, most_files, biggest, set != nullptr)) return r0;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   bool slot_used[2] = {false, false};
   std::vector<uint64_t> offs, skip_lens;
@@ -2743,7 +3027,7 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
         zp.job = std::move(jobs.front());
         zp.stage = (int)(zjobs++ % (uint64_t)hbx_ctx::kZStages);
         const double t1 = now();
-        r = z_start(c, zp, cut_ends, out_base, sums);
+        r = z_start(c, zp, cut_ends, out_base, sums, z.fresh);
         zt[1] += now() - t1;
         arena_zstage = zp.stage;
         // the unpack runs on a worker thread while this loop reads and copies
@@ -2815,7 +3099,8 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
       blens = skip_lens.data();
     }
     rc = submit_batch(c, arena.p, f - first, offs.data(), blens, cut_ends, ids,
-                      out_base + first, caps + first, sums ? sums + first : nullptr, budget);
+                      out_base + first, caps + first, sums ? sums + first : nullptr, budget, nullptr, nullptr, set,
+                      fresh);
     if (z.zout && rc == HBX_OK) jobs.push_back(ZJob{first, f - first, static_cast<const uint8_t*>(arena.p), offs});
     k++;
   }
@@ -2840,6 +3125,12 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
     }
   }
   if (rc != HBX_OK && z.zout) zsync_all();
+  // the caller saw none of a failed call's chunks: the set forgets them
+  if (rc != HBX_OK && set && !c->broken) {
+    const std::string keep = c->err;
+    (void)idset_truncate(c, set, set_count0);
+    c->err = keep;
+  }
   c->io_s[1] += now() - td;
   if (z.zout && ab_env("HBX_ZDIAG"))
     std::fprintf(stderr, "zdiag: wait_oldest %.3f s, z_start %.3f s, z_finish %.3f s (event waits %.3f s), jobs %llu\n",

@@ -59,6 +59,9 @@ class FileChunks:
     content_id: bytes  # entry.ContentBlockID
     zstreams: Optional[list] = None  # zlib stream per chunk, uint8 views (store_paths(compress=True))
     errno: int = 0  # store_paths(skip_unreadable=True): the errno of a file skipped (no chunks), else 0
+    # with dedup=IdSet: bool [k], True where the chunk's ID is the first occurrence of an ID the set
+    # did not hold (only those chunks are compressed and need sending); None without a set
+    fresh: Optional[np.ndarray] = None
 
     @property
     def n_chunks(self) -> int:
@@ -117,6 +120,105 @@ class SegmentedFile:
             e = self._engine
             e._check(e._L.hbx_seg_close(e._ctx, self._h), "hbx_seg_close")
             self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _ids_array(ids) -> np.ndarray:
+    """Block IDs as a contiguous uint8 [n, 16] array: an array of that shape,
+    raw bytes (16 per ID) or a sequence of 16-byte IDs."""
+    if isinstance(ids, np.ndarray):
+        a = np.ascontiguousarray(ids, np.uint8)
+    elif isinstance(ids, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(bytes(ids), np.uint8)
+    else:
+        a = np.frombuffer(b"".join(bytes(x) for x in ids), np.uint8)
+    if a.size % 16:
+        raise ValueError("block IDs are 16 bytes each")
+    return a.reshape(-1, 16)
+
+
+class IdSet:
+    """A set of block IDs in device memory (hbx_idset, K9): what the server
+    is known to hold.  ``Engine.store_paths(dedup=set)`` and
+    ``Engine.submit_device(dedup=set)`` consult it in submit order, report
+    per chunk whether its ID is new (``FileChunks.fresh``) and compress only
+    the new ones, in place of the reference's queue-map check and allo/ACKN
+    round (pkg/core/client.go:571-576, server/server.go:160-168)."""
+
+    def __init__(self, engine: "Engine", capacity: int):
+        self._engine = engine
+        self._h = ctypes.c_void_p()
+        engine._check(engine._L.hbx_idset_create(engine._ctx, int(capacity), ctypes.byref(self._h)),
+                      "hbx_idset_create")
+
+    def insert(self, ids) -> np.ndarray:
+        """Test-and-insert, in order: True exactly for the first occurrence of
+        an ID the set did not hold (hbx_idset_insert)."""
+        a = _ids_array(ids)
+        fresh = np.zeros(max(a.shape[0], 1), np.uint8)
+        e = self._engine
+        e._check(e._L.hbx_idset_insert(e._ctx, self._h, a.shape[0], _p(a), _p(fresh)), "hbx_idset_insert")
+        return fresh[:a.shape[0]].astype(bool)
+
+    def contains(self, ids) -> np.ndarray:
+        """True where the ID is in the set (hbx_idset_contains); reads only."""
+        a = _ids_array(ids)
+        found = np.zeros(max(a.shape[0], 1), np.uint8)
+        e = self._engine
+        e._check(e._L.hbx_idset_contains(e._ctx, self._h, a.shape[0], _p(a), _p(found)), "hbx_idset_contains")
+        return found[:a.shape[0]].astype(bool)
+
+    def _stats(self):
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        e = self._engine
+        e._check(e._L.hbx_idset_stats(e._ctx, self._h, *[ctypes.byref(x) for x in v]), "hbx_idset_stats")
+        return [int(x.value) for x in v]
+
+    @property
+    def count(self) -> int:
+        return self._stats()[0]
+
+    @property
+    def capacity(self) -> int:
+        return self._stats()[1]
+
+    @property
+    def slots(self) -> int:
+        return self._stats()[2]
+
+    @property
+    def dropped(self) -> int:
+        """IDs not inserted because the set was full (they stay fresh)."""
+        return self._stats()[3]
+
+    def export(self) -> np.ndarray:
+        """The set's IDs, uint8 [count, 16], in insertion order
+        (hbx_idset_export): call / submit order across calls and batches,
+        unspecified within one."""
+        n = self.count
+        out = np.zeros((max(n, 1), 16), np.uint8)
+        got = ctypes.c_uint64(0)
+        e = self._engine
+        e._check(e._L.hbx_idset_export(e._ctx, self._h, _p(out), n, ctypes.byref(got)), "hbx_idset_export")
+        return out[:int(got.value)]
+
+    def truncate(self, n: int):
+        """Keep the first ``n`` IDs of the export order (hbx_idset_truncate):
+        roll back to a ``count`` noted before a send that failed."""
+        e = self._engine
+        e._check(e._L.hbx_idset_truncate(e._ctx, self._h, int(n)), "hbx_idset_truncate")
+
+    def close(self):
+        """hbx_idset_destroy: refused (HbxError) while pending batches use the set."""
+        if self._h and self._engine._ctx:
+            e = self._engine
+            e._check(e._L.hbx_idset_destroy(e._ctx, self._h), "hbx_idset_destroy")
+        self._h = ctypes.c_void_p()
 
     def __enter__(self):
         return self
@@ -200,7 +302,7 @@ class Engine:
         return caps, base, cuts, ids, sums
 
     @staticmethod
-    def _unpack(lens, caps, base, cuts, ids, sums) -> List[FileChunks]:
+    def _unpack(lens, caps, base, cuts, ids, sums, fresh=None) -> List[FileChunks]:
         # one structured view of the summaries; each file's cut ends and ids
         # are views into the per-call output arrays (no per-file copies:
         # 100 k files unpack in ~0.15 s instead of ~0.4 s)
@@ -217,8 +319,13 @@ class Engine:
         was = gc.isenabled()
         gc.disable()
         try:
-            return [FileChunks(cuts[b:b + kk], ids[b:b + kk], t, cid[16 * f:16 * f + 16] if kk else b"")
-                    for f, (b, kk, t) in enumerate(zip(starts, ks, types))]
+            res = [FileChunks(cuts[b:b + kk], ids[b:b + kk], t, cid[16 * f:16 * f + 16] if kk else b"")
+                   for f, (b, kk, t) in enumerate(zip(starts, ks, types))]
+            if fresh is not None:
+                fb = fresh.astype(bool)
+                for r, b, kk in zip(res, starts, ks):
+                    r.fresh = fb[b:b + kk]
+            return res
         finally:
             if was:
                 gc.enable()
@@ -252,10 +359,13 @@ class Engine:
                                                   _p(caps), sums), "hbx_chunk_hash_device")
         return self._unpack(lens, caps, base, cuts, ids, sums)
 
-    def submit_device(self, d_arena: int, offs: Sequence[int], lens: Sequence[int]):
+    def submit_device(self, d_arena: int, offs: Sequence[int], lens: Sequence[int],
+                      dedup: Optional[IdSet] = None):
         """Enqueue a device-resident batch and return at once.  Any number of
         batches may be in flight; :meth:`wait` completes the oldest.  The
-        arena must stay untouched until then."""
+        arena must stay untouched until then.  With ``dedup`` the batch's
+        chunk IDs are marked against that set in submit order
+        (hbx_submit_device_dd) and :meth:`wait` fills ``FileChunks.fresh``."""
         self._after_producer()
         offs = np.ascontiguousarray(offs, np.uint64)
         lens = np.ascontiguousarray(lens, np.uint64)
@@ -263,6 +373,13 @@ class Engine:
         caps, base, cuts, ids, sums = self._alloc_out(lens)
         t1 = time.perf_counter()
         self.alloc_s = t1 - t0  # (bench diagnostics: host output arrays of this submit)
+        if dedup is not None:
+            fresh = np.zeros(cuts.shape[0], np.uint8)
+            self._check(self._L.hbx_submit_device_dd(self._ctx, ctypes.c_void_p(int(d_arena)), len(lens),
+                                                     _p(offs), _p(lens), _p(cuts), _p(ids), _p(base),
+                                                     _p(caps), sums, dedup._h, _p(fresh)), "hbx_submit_device_dd")
+            self._pending.append((offs, lens, caps, base, cuts, ids, sums, fresh))
+            return
         self._check(self._L.hbx_submit_device(self._ctx, ctypes.c_void_p(int(d_arena)), len(lens),
                                               _p(offs), _p(lens), _p(cuts), _p(ids), _p(base),
                                               _p(caps), sums), "hbx_submit_device")
@@ -288,8 +405,8 @@ class Engine:
         if isinstance(item[0], str):  # ("verify", ...)
             _, n, ids, ok, bad, keep = item
             return ids[:n], (ok[:n].astype(bool) if keep[1] is not None else None), int(bad.value)
-        offs, lens, caps, base, cuts, ids, sums = item
-        return self._unpack(lens, caps, base, cuts, ids, sums)
+        offs, lens, caps, base, cuts, ids, sums = item[:7]
+        return self._unpack(lens, caps, base, cuts, ids, sums, item[7] if len(item) > 7 else None)
 
     def verify_submit_device(self, d_arena: int, offs: Sequence[int], lens: Sequence[int],
                              links: Optional[Sequence[Sequence[bytes]]] = None,
@@ -575,7 +692,7 @@ class Engine:
                     on_batch: Optional[Callable[[int, int], None]] = None,
                     on_files: Optional[Callable[[int, List[FileChunks]], None]] = None,
                     sizes: Optional[Sequence[int]] = None,
-                    skip_unreadable: bool = False) -> List[FileChunks]:
+                    skip_unreadable: bool = False, dedup: Optional[IdSet] = None) -> List[FileChunks]:
         """storeFile for many files on disk, end to end: the library reads them
         into pinned memory on ``io_threads`` threads and overlaps reading the
         next batch with the copy + kernels of the current one.  With
@@ -596,7 +713,12 @@ class Engine:
         221-224) or a read failing with EBADF (minorPathError,
         hashback_unix.go:57-63) -- comes back with no chunks and its errno in
         ``FileChunks.errno``, and the rest of its batch is stored; any other
-        read error still fails the call.  ``last_call_s`` holds the library
+        read error still fails the call.  With ``dedup`` (hbx_store_paths_dd)
+        every chunk's ID is marked against that set in file order:
+        ``FileChunks.fresh`` says which chunks are new, only those are
+        compressed (the ``zstreams`` entry of any other chunk is an empty
+        view), ``batch_bytes`` is honoured down to 1 MiB, and a call that
+        fails leaves the set as it was.  ``last_call_s`` holds the library
         call's wall seconds."""
         if (on_batch is not None or on_files is not None) and not compress:
             raise ValueError("on_batch / on_files need compress=True (hbx_store_paths_zcb)")
@@ -610,6 +732,9 @@ class Engine:
         arr = (ctypes.c_char_p * max(len(enc), 1))(*enc)
         caps, base, cuts, ids, sums = self._alloc_out(lens)
         status = np.zeros(max(len(enc), 1), np.int32) if skip_unreadable else None
+        fresh = np.zeros(cuts.shape[0], np.uint8) if dedup is not None else None
+        dd_status = _p(status) if status is not None else None
+        dd_tail = (dedup._h, _p(fresh)) if dedup is not None else ()
 
         def with_status(res):
             if status is not None:
@@ -619,7 +744,12 @@ class Engine:
 
         if not compress:
             t0 = time.perf_counter()
-            if status is None:
+            if dedup is not None:
+                self._check(self._L.hbx_store_paths_dd(
+                    self._ctx, len(enc), ctypes.cast(arr, ctypes.c_void_p), _p(lens), _p(cuts), _p(ids), _p(base),
+                    _p(caps), sums, dd_status, int(io_threads), int(batch_bytes), None, None, None, None, None,
+                    None, *dd_tail), "hbx_store_paths_dd")
+            elif status is None:
                 self._check(self._L.hbx_store_paths(self._ctx, len(enc), ctypes.cast(arr, ctypes.c_void_p),
                                                     _p(lens), _p(cuts), _p(ids), _p(base), _p(caps), sums,
                                                     int(io_threads), int(batch_bytes)), "hbx_store_paths")
@@ -629,7 +759,7 @@ class Engine:
                     _p(caps), sums, _p(status), int(io_threads), int(batch_bytes), None, None, None, None, None,
                     None), "hbx_store_paths_status")
             self.last_call_s = time.perf_counter() - t0
-            return with_status(self._unpack(lens, caps, base, cuts, ids, sums))
+            return with_status(self._unpack(lens, caps, base, cuts, ids, sums, fresh))
         fb = np.array([self._L.hbx_deflate_file_bound(int(x)) for x in lens], np.uint64)
         zbase = np.zeros(max(lens.size, 1), np.uint64)
         if lens.size > 1:
@@ -648,13 +778,19 @@ class Engine:
             r.zstreams = [zout[int(zoff[b + i]):int(zoff[b + i] + zlen[b + i])] for i in range(k)]
             if status is not None:  # written when the file was read, before its batch was reported
                 r.errno = int(status[f])
+            if fresh is not None:
+                r.fresh = fresh[b:b + k].astype(bool)
             return r
 
         t0 = time.perf_counter()
         if status is not None:  # the same with per-file outcomes (hbx_store_paths_status)
             zargs_st = zargs[:9] + (_p(status),) + zargs[9:]
+        if dedup is not None:
+            zargs_st = zargs[:9] + (dd_status,) + zargs[9:]
         if on_batch is None and on_files is None:
-            if status is None:
+            if dedup is not None:
+                self._check(self._L.hbx_store_paths_dd(*zargs_st, None, None, *dd_tail), "hbx_store_paths_dd")
+            elif status is None:
                 self._check(self._L.hbx_store_paths_z(*zargs), "hbx_store_paths_z")
             else:
                 self._check(self._L.hbx_store_paths_status(*zargs_st, None, None), "hbx_store_paths_status")
@@ -672,7 +808,10 @@ class Engine:
                 except BaseException as e:  # never unwind through C
                     raised.append(e)
             cb = _lib.BATCH_READY(ready)
-            if status is None:
+            if dedup is not None:
+                self._check(self._L.hbx_store_paths_dd(*zargs_st, ctypes.cast(cb, ctypes.c_void_p), None, *dd_tail),
+                            "hbx_store_paths_dd")
+            elif status is None:
                 self._check(self._L.hbx_store_paths_zcb(*zargs, ctypes.cast(cb, ctypes.c_void_p), None),
                             "hbx_store_paths_zcb")
             else:
@@ -681,7 +820,7 @@ class Engine:
             if raised:
                 raise raised[0]
         self.last_call_s = time.perf_counter() - t0
-        res = with_status(self._unpack(lens, caps, base, cuts, ids, sums))
+        res = with_status(self._unpack(lens, caps, base, cuts, ids, sums, fresh))
         for f, r in enumerate(res):
             b = int(base[f])
             r.zstreams = [zout[int(zoff[b + i]):int(zoff[b + i] + zlen[b + i])]  # views, no copy

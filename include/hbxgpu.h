@@ -532,6 +532,81 @@ int hbx_store_paths_status(hbx_ctx *ctx, uint64_t n_files, const char *const *pa
                            uint64_t batch_bytes, uint8_t *zout, const uint64_t *zbase, uint64_t *zoff,
                            uint64_t *zlen, hbx_batch_ready_fn ready, void *user);
 
+/* ---- Block-ID set: skip the chunks already seen (K9) ------------------------
+ * The reference compresses and sends a block only once it is known to be new:
+ * StoreBlock drops an ID already in its queue map (pkg/core/client.go:571-576),
+ * the server answers allo with ACKN for a block it holds (server/server.go:
+ * 160-168), and a worker calls CompressData only for the blocks the server
+ * asked for with READ (client.go:211-214, 249-258).  hbx_idset is that
+ * knowledge as a set of 16-byte IDs in device memory, which the pipeline
+ * consults in submit order: exactly one chunk per distinct ID is FRESH, the
+ * first in submit order (file order, then chunk order, within a batch), however
+ * the files fall into batches.  A caller seeds it with what the server is known
+ * to hold (a previous backup's ID list).
+ * Layout of a set of capacity C: the IDs in insertion order, and a table of
+ * S = hbx_idset_slots(C) slots, the smallest power of two >= 2 C and at least
+ * 64.  An ID's home slot is LE64(id[0..8]) & (S - 1) (its first 8 bytes as a
+ * little-endian integer), with linear probing that wraps around.
+ * A full set never reports an ID it could not insert as seen: such an ID is
+ * counted in `dropped`, is fresh, and is fresh again the next time.  A wrong
+ * "seen" would lose data; a wrong "fresh" costs only work.
+ * The direct calls below are synchronous and, like the other synchronous
+ * calls, refused (HBX_ERR_STATE) while batches are pending; a set used with a
+ * context other than its own is HBX_ERR_ARG. */
+typedef struct hbx_idset hbx_idset;
+/* S for a capacity; 0 if the capacity is above 2^31.  Pure host arithmetic. */
+uint64_t hbx_idset_slots(uint64_t capacity);
+/* A set for up to `capacity` IDs (1..2^31): 16 bytes per ID + 4 per slot of
+ * device memory. */
+int hbx_idset_create(hbx_ctx *ctx, uint64_t capacity, hbx_idset **out);
+/* HBX_ERR_STATE while pending batches still use the set. */
+int hbx_idset_destroy(hbx_ctx *ctx, hbx_idset *set);
+/* Test-and-insert n IDs (16 n bytes, host memory) in order: fresh[i] = 1
+ * exactly for the first occurrence of an ID the set did not hold, else 0.
+ * fresh may be NULL (bulk seeding). */
+int hbx_idset_insert(hbx_ctx *ctx, hbx_idset *set, uint64_t n, const uint8_t *ids, uint8_t *fresh);
+/* Read only: found[i] = 1 iff ids[16 i ..] is in the set. */
+int hbx_idset_contains(hbx_ctx *ctx, hbx_idset *set, uint64_t n, const uint8_t *ids, uint8_t *found);
+/* Any of the outputs may be NULL.  dropped: IDs not inserted because the set
+ * was full, over the set's lifetime. */
+int hbx_idset_stats(hbx_ctx *ctx, hbx_idset *set, uint64_t *count, uint64_t *capacity, uint64_t *slots,
+                    uint64_t *dropped);
+/* The set's IDs in insertion order into ids (16 cap bytes); *n = count
+ * (HBX_ERR_CAPACITY if count > cap).  Across calls and across pipeline batches
+ * the order is call / submit order; within one call or batch it is unspecified. */
+int hbx_idset_export(hbx_ctx *ctx, hbx_idset *set, uint8_t *ids, uint64_t cap, uint64_t *n);
+/* Keep the first `count` IDs of that order and forget the rest: a caller
+ * notes the count before a send and rolls back when the send fails.
+ * count above the set's is HBX_ERR_ARG. */
+int hbx_idset_truncate(hbx_ctx *ctx, hbx_idset *set, uint64_t count);
+
+/* hbx_submit_device with a set (NULL: exactly hbx_submit_device).  With a set,
+ * fresh is required and runs parallel to ids: at the hbx_wait that completes
+ * the batch, fresh[k] = 1 where ids[16 k ..] is the first occurrence of an ID
+ * the set did not hold, and that ID is in the set; it must stay valid until
+ * then.  The mark runs on the device when the batch's last chain is hashed, in
+ * submit order (a batch with a set completes no earlier than the older batches
+ * with one).  Verify and segment batches never touch a set.  Rolling back after
+ * a failed send is the caller's job (hbx_idset_truncate). */
+int hbx_submit_device_dd(hbx_ctx *ctx, const void *d_arena, uint64_t n_files, const uint64_t *file_offs,
+                         const uint64_t *file_lens, uint64_t *cut_ends, uint8_t *ids, const uint64_t *out_base,
+                         const uint64_t *caps, hbx_file_summary *summaries, hbx_idset *set, uint8_t *fresh);
+/* hbx_store_paths_status with a set (NULL: exactly hbx_store_paths_status).
+ * status may be NULL here: every read failure then fails the call, as in
+ * hbx_store_paths.  fresh as above.  With compression, only fresh chunks are compressed, copied
+ * back and placed: a chunk that is not fresh gets zlen = 0 (no real stream is
+ * shorter than 11 bytes) and zoff = the running offset.  If the server answers
+ * READ for such a chunk after all (a stale set: the server lost a block the
+ * set was seeded with), compress it on demand with hbx_deflate_blocks.  With a
+ * set, batch_bytes is honoured down to 1 MiB (without one it is raised to
+ * 64 MiB).  If the call fails, the set is first truncated to the count it had
+ * on entry: the caller saw none of those chunks. */
+int hbx_store_paths_dd(hbx_ctx *ctx, uint64_t n_files, const char *const *paths, const uint64_t *lens,
+                       uint64_t *cut_ends, uint8_t *ids, const uint64_t *out_base, const uint64_t *caps,
+                       hbx_file_summary *summaries, int32_t *status, uint32_t io_threads, uint64_t batch_bytes,
+                       uint8_t *zout, const uint64_t *zbase, uint64_t *zoff, uint64_t *zlen,
+                       hbx_batch_ready_fn ready, void *user, hbx_idset *set, uint8_t *fresh);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
