@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libhbxgpu.so")
 
 HBX_OK = 0
 ERRORS = {-1: "HBX_ERR_ARG", -2: "HBX_ERR_HIP", -3: "HBX_ERR_CAPACITY", -4: "HBX_ERR_IO",
-          -5: "HBX_ERR_NODEV", -6: "HBX_ERR_STATE", -7: "HBX_ERR_FORMAT"}
+          -5: "HBX_ERR_NODEV", -6: "HBX_ERR_STATE", -7: "HBX_ERR_FORMAT", -8: "HBX_ERR_SINK"}
 
 # Every symbol include/hbxgpu.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -39,6 +39,7 @@ EXPORTS = [
     "hbx_seg_next", "hbx_seg_open", "hbx_seg_close", "hbx_seg_submit_device", "hbx_store_file_seg",
     "hbx_idset_slots", "hbx_idset_create", "hbx_idset_destroy", "hbx_idset_insert", "hbx_idset_contains",
     "hbx_idset_stats", "hbx_idset_export", "hbx_idset_truncate", "hbx_submit_device_dd", "hbx_store_paths_dd",
+    "hbx_seg_submit_device_dd", "hbx_store_file_stream",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -88,6 +89,20 @@ PLAN_ARENA_SLACK = 64 << 20
 
 # hbx_batch_ready_fn (include/hbxgpu.h)
 BATCH_READY = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64)
+
+STREAM_COMPRESS = 1  # HBX_STREAM_COMPRESS
+
+
+class SegChunks(ctypes.Structure):
+    """hbx_seg_chunks: what one segment of hbx_store_file_stream completed."""
+    _fields_ = [("first_chunk", ctypes.c_uint64), ("n_chunks", ctypes.c_uint64), ("cut_ends", ctypes.c_void_p),
+                ("ids", ctypes.c_void_p), ("fresh", ctypes.c_void_p), ("z", ctypes.c_void_p),
+                ("zoff", ctypes.c_void_p), ("zlen", ctypes.c_void_p), ("final", ctypes.c_int),
+                ("summary", FileSummary)]
+
+
+# hbx_seg_sink_fn (include/hbxgpu.h)
+SEG_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SegChunks))
 
 _lib = None
 
@@ -207,6 +222,8 @@ def load() -> ctypes.CDLL:
     L.hbx_idset_truncate.argtypes = [P, P, U64]
     L.hbx_submit_device_dd.argtypes = L.hbx_submit_device.argtypes + [P, P]
     L.hbx_store_paths_dd.argtypes = L.hbx_store_paths_status.argtypes + [P, P]
+    L.hbx_seg_submit_device_dd.argtypes = L.hbx_seg_submit_device.argtypes + [P, P]
+    L.hbx_store_file_stream.argtypes = [P, ctypes.c_char_p, U64, U64, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

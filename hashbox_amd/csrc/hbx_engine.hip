@@ -28,6 +28,7 @@
 #include <cstring>
 #include <deque>
 #include <future>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -146,6 +147,7 @@ struct hbx_seg {
   std::vector<uint8_t> ids;   // the file's chunk ids collected so far (the chain block's links)
   bool keep_cuts = false;     // hbx_store_file_seg: collect the cut ends here too
   std::vector<uint64_t> cuts;
+  uint64_t last_cut = 0;      // the latest collected cut end: where the next segment's first chunk starts
 };
 
 // A set of block IDs in device memory (hbx_idset_create; layout and kernels:
@@ -203,7 +205,7 @@ struct Batch {
   std::vector<hbx_seg*> segs;
   std::vector<uint64_t> seg_off;
   std::vector<uint8_t> seg_final;
-  // submitted with an ID set (hbx_submit_device_dd): K9 marks its result slots
+  // submitted with an ID set (hbx_submit_device_dd, hbx_seg_submit_device_dd): K9 marks its result slots
   // when it is finalized, dd_seq-th of the context's marks; the flags go to
   // fresh_out[out_base[f] + q] at the collect
   hbx_idset* set = nullptr;
@@ -1498,6 +1500,7 @@ int collect_segments(hbx_ctx* c, Batch* b) {
     const uint64_t k = counts[f], ib = b->cut_base[f], so = b->seg_off[f];
     h->inflight--;
     h->ids.insert(h->ids.end(), hid + 16 * ib, hid + 16 * (ib + k));
+    if (k) h->last_cut = so + cuts[ib + k - 1];
     if (h->keep_cuts)
       for (uint64_t i = 0; i < k; i++) h->cuts.push_back(so + cuts[ib + i]);
     hbx_file_summary sum{};
@@ -1514,6 +1517,8 @@ int collect_segments(hbx_ctx* c, Batch* b) {
     if (b->cut_ends)
       for (uint64_t i = 0; i < k; i++) b->cut_ends[b->out_base[f] + i] = so + cuts[ib + i];
     if (b->ids) std::memcpy(b->ids + 16 * b->out_base[f], hid + 16 * ib, k * 16);
+    // (the set's inflight count is the batch's, not the segment's: collect_batch drops it once)
+    if (b->set && b->fresh_out) std::memcpy(b->fresh_out + b->out_base[f], hr + rl.fresh + ib, k);
   }
   return rc;
 }
@@ -2382,7 +2387,8 @@ namespace {
 // handles advance only once the batch is in the FIFO.
 int seg_submit(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena, const uint64_t* arena_offs,
                const uint64_t* seg_lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
-               const uint64_t* caps, hbx_file_summary* sums, uint32_t budget) {
+               const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_idset* set = nullptr,
+               uint8_t* fresh = nullptr) {
   if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
   std::vector<uint64_t> seg_offs(n);
   for (uint64_t f = 0; f < n; f++) {
@@ -2403,7 +2409,7 @@ int seg_submit(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena
       return c->fail(HBX_ERR_CAPACITY, "segment " + std::to_string(f) + ": caps below hbx_max_chunks(seg_len)");
   }
   int rc = submit_batch(c, d_arena, n, arena_offs, seg_lens, cut_ends, ids, out_base, caps, sums, budget, segs,
-                        seg_offs.data());
+                        seg_offs.data(), set, set ? fresh : nullptr);
   if (rc) return rc;
   for (uint64_t f = 0; f < n; f++) {
     hbx_seg* h = segs[f];
@@ -2419,12 +2425,23 @@ int seg_submit(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena
 int hbx_seg_submit_device(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena,
                           const uint64_t* arena_offs, const uint64_t* seg_lens, uint64_t* cut_ends, uint8_t* ids,
                           const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums) {
+  return hbx_seg_submit_device_dd(c, n, segs, d_arena, arena_offs, seg_lens, cut_ends, ids, out_base, caps, sums,
+                                  nullptr, nullptr);
+}
+
+int hbx_seg_submit_device_dd(hbx_ctx* c, uint64_t n, hbx_seg* const* segs, const void* d_arena,
+                             const uint64_t* arena_offs, const uint64_t* seg_lens, uint64_t* cut_ends, uint8_t* ids,
+                             const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums, hbx_idset* set,
+                             uint8_t* fresh) {
   if (!c) return HBX_ERR_ARG;
   if (!n || !segs || !d_arena || !arena_offs || !seg_lens || !out_base || !caps) return HBX_ERR_ARG;
+  if (set && !fresh) return HBX_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
+  if (set && std::find(c->idsets.begin(), c->idsets.end(), set) == c->idsets.end())
+    return c->fail(HBX_ERR_ARG, "not an ID set of this context");
   HBX_TRY(c, hipSetDevice(c->device));
   return seg_submit(c, n, segs, d_arena, arena_offs, seg_lens, cut_ends, ids, out_base, caps, sums,
-                    c->md5_slice ? c->md5_slice : kBudgetAll);
+                    c->md5_slice ? c->md5_slice : kBudgetAll, set, fresh);
 }
 
 int hbx_chunk_hash_batch(hbx_ctx* c, uint64_t n, const uint8_t* const* datas,
@@ -2723,9 +2740,10 @@ struct ZPend {
                                 // which the main loop owns; zdrain_one copies it
 };
 
+int z_launch(hbx_ctx* c, int stage, std::vector<hbxz::ZBlock>& zb, uint64_t d, uint64_t nseg);
+
 int z_start(hbx_ctx* c, ZPend& zp, const uint64_t* cut_ends, const uint64_t* out_base,
             const hbx_file_summary* sums, const uint8_t* fresh) {
-  auto& Z = c->zs[zp.stage];
   std::vector<hbxz::ZBlock> zb;
   uint64_t d = 0, nseg = 0;
   for (uint64_t i = 0; i < zp.job.count; i++) {
@@ -2747,6 +2765,14 @@ int z_start(hbx_ctx* c, ZPend& zp, const uint64_t* cut_ends, const uint64_t* out
       start = e;
     }
   }
+  return z_launch(c, zp.stage, zb, d, nseg);
+}
+
+// Enqueue K7 over `zb` (dst: offsets into the stage, d bytes in all, nseg
+// 32 KiB pieces) on the stage's stream, the copy-back of the lengths and the
+// streams into its pinned buffers, and its completion event.
+int z_launch(hbx_ctx* c, int stage, std::vector<hbxz::ZBlock>& zb, uint64_t d, uint64_t nseg) {
+  auto& Z = c->zs[stage];
   const uint64_t n = zb.size();
   if (n == 0) return HBX_OK;
   if (nseg > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "too much data in one batch");
@@ -3278,6 +3304,326 @@ int hbx_store_file_seg(hbx_ctx* c, const char* path, uint64_t file_len, uint64_t
       }
     }
   }
+  const std::string keep = c->err;
+  (void)hbx_seg_close(c, h);
+  if (rc) c->err = keep;
+  return rc;
+}
+
+namespace {
+// One segment of hbx_store_file_stream, from its submit to the end of its sink
+// call: the arrays its batch is collected into, then what the sink is shown.
+struct StreamSeg {
+  uint64_t off = 0, len = 0;       // file bytes [off, off + len)
+  const uint8_t* arena = nullptr;  // the ring arena that holds them
+  size_t ring = 0;                 // its slot in the ring
+  bool final = false;
+  uint64_t first_chunk = 0, k = 0;  // index of its first chunk in the file; chunks it completed
+  uint64_t prev_cut = 0;            // where its first chunk starts: the file's previous last cut end
+  std::vector<uint64_t> cuts, zoff, zlen;
+  std::vector<uint8_t> ids, fresh;
+  hbx_file_summary sum{};
+  int stage = -1;             // its compression stage (-1: none)
+  bool zstarted = false;      // K7 of it is on the stage's stream
+  std::vector<uint64_t> dst;  // stage offset of each chunk's stream (kNoStream: not compressed)
+  std::shared_future<int> fin;  // its worker: waits for the stage, then runs the sink
+  std::string err;              // the worker's error text (never c->err, which the main loop owns)
+};
+
+// The worker's part: wait for the segment's compression job, lay out zoff and
+// zlen over the pinned stage, and show the segment to the sink.
+int stream_finish(const hbx_ctx* c, StreamSeg& s, bool zip, hbx_seg_sink_fn sink, void* user) {
+  const uint8_t* z = nullptr;
+  if (zip) {
+    const auto& Z = c->zs[s.stage];
+    if (s.zstarted) {
+      (void)hipSetDevice(c->device);
+      const hipError_t e = hipEventSynchronize(Z.done);
+      if (e != hipSuccess) {
+        s.err = std::string("hipEventSynchronize(compression stage): ") + hipGetErrorString(e);
+        return HBX_ERR_HIP;
+      }
+    }
+    // (the stage's length list holds the compressed chunks only, in order: zi)
+    const uint64_t* ol = Z.lens.as<uint64_t>();
+    uint64_t run = 0, zi = 0;
+    for (uint64_t i = 0; i < s.k; i++) {
+      const bool has = s.dst[i] != kNoStream;
+      s.zoff[i] = has ? s.dst[i] : run;
+      s.zlen[i] = has ? ol[zi++] : 0;
+      run = s.zoff[i] + s.zlen[i];
+    }
+    z = Z.stage.as<uint8_t>();
+  }
+  if (!sink) return HBX_OK;
+  hbx_seg_chunks sc{};
+  sc.first_chunk = s.first_chunk;
+  sc.n_chunks = s.k;
+  sc.cut_ends = s.cuts.data();
+  sc.ids = s.ids.data();
+  sc.fresh = s.fresh.empty() ? nullptr : s.fresh.data();
+  sc.z = z;
+  sc.zoff = zip ? s.zoff.data() : nullptr;
+  sc.zlen = zip ? s.zlen.data() : nullptr;
+  sc.final = s.final ? 1 : 0;
+  sc.summary = s.sum;
+  if (const int rv = sink(user, &sc)) {
+    s.err = "the sink returned " + std::to_string(rv) + " for the segment at file offset " + std::to_string(s.off);
+    return HBX_ERR_SINK;
+  }
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_store_file_stream(hbx_ctx* c, const char* path, uint64_t file_len, uint64_t seg_bytes, uint32_t io_threads,
+                          uint32_t flags, hbx_idset* set, hbx_seg_sink_fn sink, void* user,
+                          hbx_file_summary* summary) {
+  // (every argument check that needs no context comes before the context is touched)
+  if (!c || !path) return HBX_ERR_ARG;
+  if (seg_bytes < HBX_SEG_MIN_BYTES || seg_bytes % HBX_ARENA_ALIGN) return HBX_ERR_ARG;
+  if (flags & ~HBX_STREAM_COMPRESS) return HBX_ERR_ARG;
+  const bool zip = (flags & HBX_STREAM_COMPRESS) != 0;
+  if (zip && !sink) return HBX_ERR_ARG;
+  hbx_seg* h = nullptr;
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    if (set && std::find(c->idsets.begin(), c->idsets.end(), set) == c->idsets.end())
+      return c->fail(HBX_ERR_ARG, "not an ID set of this context");
+    if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  }
+  int rc = hbx_seg_open(c, file_len, &h);
+  if (rc) return rc;
+  hbx_file_summary file_sum{};
+  {
+    std::lock_guard<std::mutex> g(c->mu);
+    rc = [&]() -> int {
+      if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+      HBX_TRY(c, hipSetDevice(c->device));
+      uint64_t set_count0 = 0;  // a failed call puts the set back to this
+      if (set)
+        if (int r0 = idset_count(c, set, &set_count0, nullptr)) return r0;
+      for (hipEvent_t& e : c->h2d_done)
+        if (!e) HBX_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      // Every buffer is sized by the segment, never by the file (hbxgpu.h)
+      const uint32_t budget = c->md5_slice ? c->md5_slice : kBudgetAll;
+      const size_t depth = ring_depth(c, budget);
+      const uint64_t slot_bytes = std::min(seg_bytes, file_len) + 65536;
+      if (c->d_ring.size() < depth) c->d_ring.resize(depth);
+      for (PinBuf& p : c->h_read) HBX_TRY(c, p.ensure(slot_bytes));
+      for (size_t i = 0; i < depth; i++)
+        if (int r0 = ensure_shared(c, c->d_ring[i], slot_bytes)) return r0;
+      if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, 1, slot_bytes, set != nullptr)) return r0;
+      if (zip) {  // both stages sized once, for one segment (the bounds of store_paths_impl)
+        const uint64_t nch = max_chunks(slot_bytes), nsg = slot_bytes / hbxz::kSeg + nch;
+        const uint64_t zbytes = slot_bytes + 5ull * (slot_bytes / hbxz::kSeg) + 31ull * nch + 64;
+        for (auto& Z : c->zs) {
+          HBX_TRY(c, Z.out.ensure(zbytes));
+          HBX_TRY(c, Z.stage.ensure(zbytes));
+          HBX_TRY(c, Z.desc.ensure(nch * sizeof(hbxz::ZBlock)));
+          HBX_TRY(c, Z.lens.ensure(nch * 8));
+          HBX_TRY(c, Z.blk.ensure(nch * sizeof(hbxz::ZBlock)));
+          HBX_TRY(c, Z.info.ensure(nsg * sizeof(hbxz::SegInfo)));
+          HBX_TRY(c, Z.off.ensure(nsg * 8));
+          HBX_TRY(c, Z.len.ensure(nch * 8));
+          HBX_TRY(c, Z.img.ensure(nsg * hbxz::kSlot));
+        }
+      }
+      const int fd = file_len ? ::open(path, O_RDONLY | O_CLOEXEC) : -1;
+      if (file_len && fd < 0)
+        return c->fail(HBX_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+      auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+      // `flying`: submitted, not yet collected (the context's FIFO, in order);
+      // `sinking`: collected, its worker not yet joined (at most one per stage)
+      std::deque<std::unique_ptr<StreamSeg>> flying, sinking;
+      std::vector<int> ring_stage(depth, -1);  // the stage whose job last read the arena
+      std::atomic<int> worker_rc{0};           // the first failure of a worker
+      uint64_t chunks_done = 0, zjobs = 0;
+      bool from_worker = false;
+      auto sdrain_one = [&]() -> int {
+        const int r = sinking.front()->fin.get();
+        if (r && !sinking.front()->err.empty()) c->err = sinking.front()->err;  // the worker's text, on this thread
+        sinking.pop_front();
+        return r;
+      };
+      // Collect the oldest segment and hand it to a worker: its compression job
+      // goes on a stage's stream first, so the job and the sink call overlap
+      // the reading, copying and hashing of the segments behind it.
+      auto collect = [&]() -> int {
+        StreamSeg* s = flying.front().get();
+        s->prev_cut = h->last_cut;  // (the collect moves it on)
+        int r = wait_oldest(c);
+        if (r) return r;  // (the segment keeps its arrays until nothing is pending)
+        std::unique_ptr<StreamSeg> u = std::move(flying.front());
+        flying.pop_front();
+        s->k = s->sum.n_chunks;
+        s->first_chunk = chunks_done;
+        chunks_done += s->k;
+        if (s->final) {
+          s->sum.n_chunks = (uint32_t)chunks_done;
+          file_sum = s->sum;
+        } else {
+          s->sum = hbx_file_summary{};
+        }
+        while (!r && sinking.size() >= (size_t)hbx_ctx::kZStages) r = sdrain_one();  // the stage this one takes
+        if (!r && zip) {
+          s->stage = (int)(zjobs++ % (uint64_t)hbx_ctx::kZStages);
+          std::vector<hbxz::ZBlock> zb;
+          uint64_t d = 0, nseg = 0, start = s->prev_cut;
+          for (uint64_t i = 0; i < s->k && !r; i++) {
+            const uint64_t e = s->cuts[i];
+            // a chunk lies inside its segment: it starts in the overlap at the earliest
+            if (start < s->off || e < start || e > s->off + s->len) {
+              r = c->fail(HBX_ERR_STATE, "a chunk outside its segment (internal)");
+              break;
+            }
+            const uint64_t len = e - start, ns = (len + hbxz::kSeg - 1) / hbxz::kSeg;
+            if (set && !s->fresh[i]) {  // seen before: nothing is sent for it
+              s->dst.push_back(kNoStream);
+            } else {
+              zb.push_back(hbxz::ZBlock{reinterpret_cast<uint64_t>(s->arena + (start - s->off)), d, len,
+                                        (uint32_t)nseg, (uint32_t)ns});
+              s->dst.push_back(d);
+              d += (hbx_deflate_bound(len) + 15) & ~uint64_t(15);
+              nseg += ns;
+            }
+            start = e;
+          }
+          if (!r && !zb.empty()) {
+            s->zstarted = true;
+            ring_stage[s->ring] = s->stage;
+            r = z_launch(c, s->stage, zb, d, nseg);
+          }
+        }
+        if (r) return r;
+        std::shared_future<int> prev = sinking.empty() ? std::shared_future<int>() : sinking.back()->fin;
+        sinking.push_back(std::move(u));
+        s->fin = std::async(std::launch::async, [c, s, prev, zip, sink, user, &worker_rc]() -> int {
+                   if (prev.valid()) {  // FIFO: one sink call at a time, in segment order
+                     const int r0 = prev.get();
+                     if (r0) return r0;
+                   }
+                   const int r1 = stream_finish(c, *s, zip, sink, user);
+                   if (r1) {
+                     int none = 0;
+                     worker_rc.compare_exchange_strong(none, r1);
+                   }
+                   return r1;
+                 }).share();
+        return HBX_OK;
+      };
+      bool slot_used[2] = {false, false};
+      const uint64_t zero = 0;
+      uint64_t prev_end = 0, k = 0;
+      int r = HBX_OK;
+      for (bool more = true; more && r == HBX_OK; k++) {
+        if ((r = worker_rc.load())) {  // a sink or a stage failed: read no further
+          from_worker = true;
+          break;
+        }
+        uint64_t off = 0, len = 0;
+        if ((r = hbx_seg_next(file_len, seg_bytes, prev_end, &off, &len))) {
+          r = c->fail(r, "segment layout (internal)");
+          break;
+        }
+        prev_end = off + len;
+        more = prev_end < file_len;
+        const int p = (int)(k & 1);
+        const size_t ring = (size_t)(k % depth);
+        DevBuf& arena = c->d_ring[ring];
+        const double t0 = now();
+        while (r == HBX_OK && flying.size() >= depth) r = collect();  // frees arena k % depth
+        if (r) break;
+        const double t1 = now();
+        if (slot_used[p] && (r = c->hip(hipEventSynchronize(c->h2d_done[p]), "h2d wait"))) break;
+        const double t2 = now();
+        if (len) r = read_range(fd, path, off, len, c->h_read[p].as<uint8_t>(), std::max(1u, io_threads), c->err);
+        c->io_s[0] += now() - t2;
+        c->io_s[1] += t1 - t0;
+        c->io_s[2] += t2 - t1;
+        if (r) break;
+        // the arena's previous segment may still be read by its compression job
+        if (ring_stage[ring] >= 0 &&
+            (r = c->hip(hipStreamWaitEvent(c->stream, c->zs[ring_stage[ring]].done, 0), "hipStreamWaitEvent")))
+          break;
+        ring_stage[ring] = -1;
+        if (len) {
+          const auto tc = std::chrono::steady_clock::now();
+          if ((r = c->hip(hipMemcpyAsync(arena.p, c->h_read[p].p, len, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync")))
+            break;
+          c->max_copy_ms = std::max(c->max_copy_ms, ms_since(tc));
+          if ((r = c->hip(hipEventRecord(c->h2d_done[p], c->stream), "hipEventRecord"))) break;
+          slot_used[p] = true;
+        }
+        const uint64_t scap = max_chunks(len);
+        std::unique_ptr<StreamSeg> u(new StreamSeg());
+        StreamSeg* s = u.get();
+        s->off = off;
+        s->len = len;
+        s->arena = arena.as<uint8_t>();
+        s->ring = ring;
+        s->final = !more;
+        s->cuts.resize(scap);
+        s->ids.resize(16 * scap);
+        if (set) s->fresh.resize(scap);
+        if (zip) {
+          s->zoff.resize(scap);
+          s->zlen.resize(scap);
+        }
+        r = seg_submit(c, 1, &h, arena.p, &zero, &len, s->cuts.data(), s->ids.data(), &zero, &scap, &s->sum, budget,
+                       set, set ? s->fresh.data() : nullptr);
+        if (r) break;
+        flying.push_back(std::move(u));
+        // hand over every segment whose results have already reached the host
+        // (never waiting: neither for the device nor for a busy sink)
+        while (r == HBX_OK && !flying.empty()) {
+          const Batch* b = c->pending.front();
+          if (!b->finalized || hipEventQuery(b->ev[4]) != hipSuccess) break;
+          if (sinking.size() >= (size_t)hbx_ctx::kZStages &&
+              sinking.front()->fin.wait_for(std::chrono::seconds(0)) != std::future_status::ready)
+            break;
+          r = collect();
+        }
+      }
+      if (fd >= 0) ::close(fd);
+      // collect everything in flight, also after a failure (the batches write
+      // into the segments' arrays, which live until nothing is pending)
+      const double td = now();
+      while (!c->pending.empty()) {
+        const std::string keep = c->err;
+        const int r2 = r == HBX_OK ? collect() : wait_oldest(c);
+        if (r == HBX_OK) r = r2;
+        else c->err = keep;
+      }
+      flying.clear();
+      // every worker joined (also after a failure: the stages and the arenas
+      // must be idle when this call returns)
+      while (!sinking.empty()) {
+        if (r == HBX_OK) {
+          r = sdrain_one();
+        } else {
+          const int w = sinking.front()->fin.get();
+          if (w && from_worker && !sinking.front()->err.empty()) {
+            c->err = sinking.front()->err;
+            from_worker = false;
+          }
+          sinking.pop_front();
+        }
+      }
+      if (r != HBX_OK && zip)
+        for (auto& Z : c->zs)
+          if (Z.stream) (void)hipStreamSynchronize(Z.stream);
+      // the set forgets a failed call's chunks: what a sink already shipped is
+      // fresh again next time, which costs only work
+      if (r != HBX_OK && set && !c->broken) {
+        const std::string keep = c->err;
+        (void)idset_truncate(c, set, set_count0);
+        c->err = keep;
+      }
+      c->io_s[1] += now() - td;
+      return r;
+    }();
+  }
+  if (rc == HBX_OK && summary) *summary = file_sum;
   const std::string keep = c->err;
   (void)hbx_seg_close(c, h);
   if (rc) c->err = keep;

@@ -72,6 +72,14 @@ class FileChunks:
         return starts, self.cut_ends
 
 
+@dataclass(slots=True)
+class SegmentChunks:
+    """What ``Engine.store_file(..., on_segment=...)`` hands over per segment."""
+    first_chunk: int  # index in the file of this segment's first chunk
+    chunks: FileChunks  # the chunks this segment completed (absolute cut ends); views, valid during the callback
+    final: bool  # the file's last segment: chunks.content_type / content_id are the whole file's
+
+
 def _u8(data: BytesLike) -> np.ndarray:
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data.reshape(-1).view(np.uint8))
@@ -144,8 +152,9 @@ def _ids_array(ids) -> np.ndarray:
 
 class IdSet:
     """A set of block IDs in device memory (hbx_idset, K9): what the server
-    is known to hold.  ``Engine.store_paths(dedup=set)`` and
-    ``Engine.submit_device(dedup=set)`` consult it in submit order, report
+    is known to hold.  ``Engine.store_paths(dedup=set)``,
+    ``Engine.store_file(segment_bytes=..., dedup=set)``, ``Engine.submit_device(dedup=set)`` and
+    ``Engine.seg_submit_device(dedup=set)`` consult it in submit order, report
     per chunk whether its ID is new (``FileChunks.fresh``) and compress only
     the new ones, in place of the reference's queue-map check and allo/ACKN
     round (pkg/core/client.go:571-576, server/server.go:160-168)."""
@@ -397,11 +406,16 @@ class Engine:
         self.wait_s += time.perf_counter() - t  # time inside hbx_wait (bench diagnostics)
         self._check(rc, "hbx_wait")
         if isinstance(item[0], str) and item[0] == "seg":
-            _, lens, caps, base, cuts, ids, sums, _keep = item
+            _, lens, caps, base, cuts, ids, sums, keep = item
             sv = np.ctypeslib.as_array(sums)[:len(lens)]
-            return [FileChunks(cuts[b:b + k], ids[b:b + k], int(t), bytes(c.tobytes()) if t else b"")
-                    for b, k, t, c in zip(base.astype(np.int64).tolist(), sv["n_chunks"].tolist(),
-                                          sv["content_type"].tolist(), sv["content_id"])]
+            res = [FileChunks(cuts[b:b + k], ids[b:b + k], int(t), bytes(c.tobytes()) if t else b"")
+                   for b, k, t, c in zip(base.astype(np.int64).tolist(), sv["n_chunks"].tolist(),
+                                         sv["content_type"].tolist(), sv["content_id"])]
+            if len(keep) > 2:  # submitted with a set: the K9 flags
+                fb = keep[2].astype(bool)
+                for r, b in zip(res, base.astype(np.int64).tolist()):
+                    r.fresh = fb[b:b + r.n_chunks]
+            return res
         if isinstance(item[0], str):  # ("verify", ...)
             _, n, ids, ok, bad, keep = item
             return ids[:n], (ok[:n].astype(bool) if keep[1] is not None else None), int(bad.value)
@@ -843,11 +857,37 @@ class Engine:
         return np.array(list(s), np.float64)
 
     def store_file(self, path: Union[str, os.PathLike], segment_bytes: Optional[int] = None,
-                   io_threads: int = 16) -> FileChunks:
+                   io_threads: int = 16, compress: bool = False, dedup: Optional[IdSet] = None,
+                   on_segment: Optional[Callable[["SegmentChunks"], None]] = None) -> FileChunks:
         """storeFile(path) for a regular file on disk (store.go:84-199).  With
         ``segment_bytes`` the file streams through the pipeline in segments of
         that size (hbx_store_file_seg): host and device memory then depend on
-        the segment size only, so a file may be larger than device memory."""
+        the segment size only, so a file may be larger than device memory.
+
+        ``compress``, ``dedup`` and ``on_segment`` (any of them needs
+        ``segment_bytes``) make it the sender's path (hbx_store_file_stream):
+        with ``dedup`` every chunk is marked against that set in the segment
+        that completes it (``FileChunks.fresh``), with ``compress`` every fresh
+        chunk (every chunk without a set) is zlib-compressed on the device, and
+        ``on_segment(seg)`` runs once per segment, in order, as soon as that
+        segment's chunks are ready, while later segments are still read and
+        hashed.  ``seg`` is a :class:`SegmentChunks`; the arrays of its
+        ``chunks`` (cut ends, ids, ``fresh``, ``zstreams``) are views into the
+        engine's buffers, valid only during the callback.  It must not call
+        this engine.  An exception raised in it stops the call (no later
+        segment is handed over), puts the set back to its count on entry and
+        is re-raised here.
+        With ``on_segment`` the returned FileChunks carries cut ends, ids,
+        ``fresh`` and the content id, and ``zstreams`` is None: memory stays
+        bounded by the segment size (plus 25 bytes per chunk).  Without it the
+        binding copies every segment's results, and the returned FileChunks
+        has ``fresh`` and ``zstreams`` for the whole file: convenient, but NOT
+        memory-bounded (the compressed file is held in host memory)."""
+        if compress or dedup is not None or on_segment is not None:
+            if segment_bytes is None:
+                raise ValueError("compress / dedup / on_segment need segment_bytes (hbx_store_file_stream)")
+            return self._store_file_stream(path, int(segment_bytes), int(io_threads), bool(compress), dedup,
+                                           on_segment)
         if segment_bytes is None:
             with open(path, "rb") as fh:
                 data = np.fromfile(fh, dtype=np.uint8)
@@ -861,6 +901,70 @@ class Engine:
                                                _p(cuts), _p(ids), cap, ctypes.byref(s)), "hbx_store_file_seg")
         k = int(s.n_chunks)
         return FileChunks(cuts[:k], ids[:k], int(s.content_type), bytes(s.content_id) if k else b"")
+
+    def _store_file_stream(self, path, segment_bytes: int, io_threads: int, compress: bool,
+                           dedup: Optional[IdSet], on_segment) -> FileChunks:
+        n = os.stat(path).st_size
+        cuts_l, ids_l, fresh_l, z_l = [], [], [], []
+        raised = []
+
+        def at(ptr, nbytes: int) -> np.ndarray:  # the bytes at a C pointer, not copied
+            if not ptr or nbytes == 0:
+                return np.zeros(0, np.uint8)
+            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(ptr), np.uint8)
+
+        def sink(_user, p):
+            if raised:
+                return 1
+            try:
+                s = p.contents
+                k = int(s.n_chunks)
+                cuts = at(s.cut_ends, 8 * k).view(np.uint64)
+                ids = at(s.ids, 16 * k).reshape(-1, 16)
+                fresh = at(s.fresh, k).astype(bool) if dedup is not None else None
+                zs = None
+                if compress:
+                    zoff = at(s.zoff, 8 * k).view(np.uint64).tolist()
+                    zlen = at(s.zlen, 8 * k).view(np.uint64).tolist()
+                    zv = at(s.z, max((o + ln for o, ln in zip(zoff, zlen)), default=0))
+                    zs = [zv[o:o + ln] for o, ln in zip(zoff, zlen)]
+                final = bool(s.final)
+                cuts_l.append(cuts.copy())
+                ids_l.append(ids.copy())
+                if fresh is not None:
+                    fresh_l.append(fresh)
+                if on_segment is None:
+                    if zs is not None:
+                        z_l.extend(z.copy() for z in zs)
+                    return 0
+                ctype = int(s.summary.content_type) if final else 0
+                cid = bytes(s.summary.content_id) if final and int(s.summary.n_chunks) else b""
+                on_segment(SegmentChunks(int(s.first_chunk), FileChunks(cuts, ids, ctype, cid, zs, 0, fresh), final))
+                return 0
+            except BaseException as e:  # never unwind through C: a non-zero return, re-raised below
+                raised.append(e)
+                return 1
+
+        cb = _lib.SEG_SINK(sink)
+        s = _lib.FileSummary()
+        t0 = time.perf_counter()
+        rc = self._L.hbx_store_file_stream(self._ctx, os.fsencode(path), n, segment_bytes, io_threads,
+                                           _lib.STREAM_COMPRESS if compress else 0,
+                                           dedup._h if dedup is not None else None,
+                                           ctypes.cast(cb, ctypes.c_void_p), None, ctypes.byref(s))
+        self.last_call_s = time.perf_counter() - t0
+        if raised:
+            raise raised[0]
+        self._check(rc, "hbx_store_file_stream")
+        k = int(s.n_chunks)
+        res = FileChunks(np.concatenate(cuts_l) if cuts_l else np.zeros(0, np.uint64),
+                         np.concatenate(ids_l) if ids_l else np.zeros((0, 16), np.uint8),
+                         int(s.content_type), bytes(s.content_id) if k else b"")
+        if dedup is not None:
+            res.fresh = np.concatenate(fresh_l) if fresh_l else np.zeros(0, bool)
+        if compress and on_segment is None:
+            res.zstreams = z_l
+        return res
 
     # ---------------------------------------------------- segmented files --
     @staticmethod
@@ -883,14 +987,19 @@ class Engine:
         return SegmentedFile(self, h.value, file_len)
 
     def seg_submit_device(self, files: Sequence[SegmentedFile], d_arena: int, arena_offs: Sequence[int],
-                          seg_lens: Sequence[int], seg_offs: Optional[Sequence[int]] = None):
+                          seg_lens: Sequence[int], seg_offs: Optional[Sequence[int]] = None,
+                          dedup: Optional[IdSet] = None):
         """Enqueue one batch holding the next segment of each of ``files``
         (distinct open files), resident at ``d_arena + arena_offs[i]``
         (hbx_seg_submit_device).  ``seg_offs`` (optional) are the file offsets
         the caller filled the arenas from; they are checked against what each
         handle expects (ValueError).  :meth:`wait` returns one FileChunks per
         segment: absolute cut ends, this segment's chunks, content type 0 for
-        a non-final segment and the whole file's type and id for the final."""
+        a non-final segment and the whole file's type and id for the final.
+        With ``dedup`` (hbx_seg_submit_device_dd) the chunks each segment
+        completes are marked against that set, in one submit order with
+        ``submit_device(dedup=...)`` batches, and :meth:`wait` fills
+        ``FileChunks.fresh`` per segment."""
         self._after_producer()
         offs = np.ascontiguousarray(arena_offs, np.uint64)
         lens = np.ascontiguousarray(seg_lens, np.uint64)
@@ -903,13 +1012,21 @@ class Engine:
                     raise ValueError(f"segment offset {int(o)}: the file's next segment starts at {want}")
         caps, base, cuts, ids, sums = self._alloc_out(lens)
         hs = (ctypes.c_void_p * max(len(files), 1))(*[f._h for f in files])
-        self._check(self._L.hbx_seg_submit_device(self._ctx, len(files), hs, ctypes.c_void_p(int(d_arena)), _p(offs),
-                                                  _p(lens), _p(cuts), _p(ids), _p(base), _p(caps), sums),
-                    "hbx_seg_submit_device")
+        keep = (offs, hs)
+        if dedup is not None:
+            fresh = np.zeros(cuts.shape[0], np.uint8)
+            keep = (offs, hs, fresh)
+            self._check(self._L.hbx_seg_submit_device_dd(
+                self._ctx, len(files), hs, ctypes.c_void_p(int(d_arena)), _p(offs), _p(lens), _p(cuts), _p(ids),
+                _p(base), _p(caps), sums, dedup._h, _p(fresh)), "hbx_seg_submit_device_dd")
+        else:
+            self._check(self._L.hbx_seg_submit_device(self._ctx, len(files), hs, ctypes.c_void_p(int(d_arena)),
+                                                      _p(offs), _p(lens), _p(cuts), _p(ids), _p(base), _p(caps),
+                                                      sums), "hbx_seg_submit_device")
         for f, ln in zip(files, lens.tolist()):
             f.end = (f.end - SEG_OVERLAP if f.end else 0) + int(ln)
             f.final_sent = f.end == f.file_len
-        self._pending.append(("seg", lens, caps, base, cuts, ids, sums, (offs, hs)))
+        self._pending.append(("seg", lens, caps, base, cuts, ids, sums, keep))
 
     def chunk_hash_segmented(self, data: BytesLike, segment_bytes: int, return_segments: bool = False):
         """storeFile over one in-memory file, streamed through a ring of three

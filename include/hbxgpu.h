@@ -586,8 +586,9 @@ int hbx_idset_truncate(hbx_ctx *ctx, hbx_idset *set, uint64_t count);
  * the set did not hold, and that ID is in the set; it must stay valid until
  * then.  The mark runs on the device when the batch's last chain is hashed, in
  * submit order (a batch with a set completes no earlier than the older batches
- * with one).  Verify and segment batches never touch a set.  Rolling back after
- * a failed send is the caller's job (hbx_idset_truncate). */
+ * with one).  Verify batches never touch a set; segment batches take one through
+ * hbx_seg_submit_device_dd.  Rolling back after a failed send is the caller's
+ * job (hbx_idset_truncate). */
 int hbx_submit_device_dd(hbx_ctx *ctx, const void *d_arena, uint64_t n_files, const uint64_t *file_offs,
                          const uint64_t *file_lens, uint64_t *cut_ends, uint8_t *ids, const uint64_t *out_base,
                          const uint64_t *caps, hbx_file_summary *summaries, hbx_idset *set, uint8_t *fresh);
@@ -606,6 +607,81 @@ int hbx_store_paths_dd(hbx_ctx *ctx, uint64_t n_files, const char *const *paths,
                        hbx_file_summary *summaries, int32_t *status, uint32_t io_threads, uint64_t batch_bytes,
                        uint8_t *zout, const uint64_t *zbase, uint64_t *zoff, uint64_t *zlen,
                        hbx_batch_ready_fn ready, void *user, hbx_idset *set, uint8_t *fresh);
+
+/* ---- Segments with a set: one file of any size, deduplicated and compressed --
+ * hbx_seg_submit_device with a set (NULL: exactly hbx_seg_submit_device).  With
+ * a set, fresh is required, runs parallel to ids (fresh[out_base[i] + q] for
+ * chunk q of segment i) and must stay valid until the hbx_wait that completes
+ * the batch.  A chunk is marked in the segment that COMPLETES it.  Segment
+ * batches and hbx_submit_device_dd batches share one submit order per context:
+ * exactly one chunk per distinct ID is fresh, the first in submit order
+ * (segment order within a batch, then chunk order), however segments and
+ * ordinary batches interleave.  Closing a file before its final segment leaves
+ * what its segments inserted in the set; rolling back is the caller's job
+ * (hbx_idset_truncate).  A set of another context is HBX_ERR_ARG;
+ * hbx_idset_destroy is refused while such a batch is pending. */
+int hbx_seg_submit_device_dd(hbx_ctx *ctx, uint64_t n, hbx_seg *const *segs, const void *d_arena,
+                             const uint64_t *arena_offs, const uint64_t *seg_lens, uint64_t *cut_ends,
+                             uint8_t *ids, const uint64_t *out_base, const uint64_t *caps,
+                             hbx_file_summary *summaries, hbx_idset *set, uint8_t *fresh);
+
+#define HBX_ERR_SINK (-8)          /* the sink returned non-zero */
+#define HBX_STREAM_COMPRESS 1u
+/* What one segment of hbx_store_file_stream completed. */
+typedef struct {
+  uint64_t first_chunk;      /* index in the file of this segment's first chunk */
+  uint64_t n_chunks;         /* chunks this segment completed */
+  const uint64_t *cut_ends;  /* absolute file offsets */
+  const uint8_t *ids;        /* 16 n_chunks bytes */
+  const uint8_t *fresh;      /* NULL without a set */
+  const uint8_t *z;          /* NULL without HBX_STREAM_COMPRESS: base of this segment's zlib streams */
+  const uint64_t *zoff, *zlen; /* stream i = z[zoff[i] .. + zlen[i]); zlen 0 for a chunk that is not fresh */
+  int final;                 /* 1 for the file's last segment */
+  hbx_file_summary summary;  /* final: the whole file's content type, id and chunk count (else zero) */
+} hbx_seg_chunks;
+typedef int (*hbx_seg_sink_fn)(void *user, const hbx_seg_chunks *seg);
+/* hbx_store_file_seg for a sender: storeFile(path) for a file of any size, with
+ * the set consulted per segment (set may be NULL) and, with
+ * HBX_STREAM_COMPRESS in flags, CompressData of every fresh chunk (of every
+ * chunk without a set), each segment's finished chunks handed to `sink` as
+ * soon as they are ready.
+ * The sink runs once per segment, in segment order, one call at a time, on an
+ * engine worker thread, and every call happens before this function returns.
+ * It runs as soon as that segment's cut ends, IDs, flags and streams exist,
+ * while later segments are still read, copied and hashed (a segment is
+ * collected as soon as its results have reached the host, not only when its
+ * arena is needed again).  Every pointer of *seg is valid only during the
+ * call.  The streams are read in place from the engine's pinned compression
+ * stage: nothing is copied into a caller buffer.  A stage is reused only after
+ * its sink call has returned, so at most two segments wait for the sink while
+ * the pipeline runs on.  The sink must not call into the same context.  An
+ * empty file gives one call with n_chunks == 0 and final == 1.  sink may be
+ * NULL without HBX_STREAM_COMPRESS (the set is filled and *summary written).
+ * Failures: a non-zero return from the sink fails the call with HBX_ERR_SINK
+ * (no later segment reaches the sink), a short read with HBX_ERR_IO, anything
+ * else as hbx_store_file_seg.  In every failing case the pipeline is drained
+ * (hbx_pending is 0 afterwards), a given set is first truncated to the count it
+ * had on entry (chunks a sink already shipped are then fresh again, which costs
+ * only work) and the context stays usable.  HBX_ERR_ARG for a NULL ctx or
+ * path, a bad seg_bytes (as hbx_seg_next), unknown flags, HBX_STREAM_COMPRESS
+ * without a sink (all before the context is touched) or a set of another
+ * context; HBX_ERR_STATE while batches are pending.  *summary (may be NULL)
+ * receives the file's summary.
+ * Memory bound, none of it depending on file_len: with S = min(seg_bytes,
+ * file_len) + 64 KiB, two pinned read slots of S; D ring arenas of S and the
+ * pipeline's per-batch buffers for D + 2 batches of S bytes, D being the ring
+ * depth hbx_store_paths uses (as hbx_store_file_seg); with
+ * HBX_STREAM_COMPRESS the two compression stages sized for one segment (output
+ * and pinned stage of about S each, plus 96 KiB of scratch per 32 KiB of S, as
+ * hbx_store_paths_z documents); and 41 bytes of pageable host memory per
+ * possible chunk (S / 64 KiB + 1) of each of the up to D + 3 segments between
+ * submit and the end of their sink call.  What grows with the file is only the
+ * handle's 16 bytes per chunk for the final FileChainBlock (and 48 bytes per
+ * chunk while its ID is hashed); no cut end is kept.
+ * Synchronous. */
+int hbx_store_file_stream(hbx_ctx *ctx, const char *path, uint64_t file_len, uint64_t seg_bytes,
+                          uint32_t io_threads, uint32_t flags, hbx_idset *set,
+                          hbx_seg_sink_fn sink, void *user, hbx_file_summary *summary);
 
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
