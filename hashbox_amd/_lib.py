@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(HERE, "libhbxgpu.so")
 
 HBX_OK = 0
 ERRORS = {-1: "HBX_ERR_ARG", -2: "HBX_ERR_HIP", -3: "HBX_ERR_CAPACITY", -4: "HBX_ERR_IO",
-          -5: "HBX_ERR_NODEV", -6: "HBX_ERR_STATE", -7: "HBX_ERR_FORMAT", -8: "HBX_ERR_SINK"}
+          -5: "HBX_ERR_NODEV", -6: "HBX_ERR_STATE", -7: "HBX_ERR_FORMAT", -8: "HBX_ERR_SINK", -9: "HBX_ERR_VERIFY"}
 
 # Every symbol include/hbxgpu.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -40,10 +40,12 @@ EXPORTS = [
     "hbx_idset_slots", "hbx_idset_create", "hbx_idset_destroy", "hbx_idset_insert", "hbx_idset_contains",
     "hbx_idset_stats", "hbx_idset_export", "hbx_idset_truncate", "hbx_submit_device_dd", "hbx_store_paths_dd",
     "hbx_seg_submit_device_dd", "hbx_store_file_stream",
+    "hbx_restore_in_bound", "hbx_restore_blocks", "hbx_restore_file_stream",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
-               "hbx_directory_block_size", "hbx_deflate_bound", "hbx_deflate_file_bound", "hbx_idset_slots")
+               "hbx_directory_block_size", "hbx_deflate_bound", "hbx_deflate_file_bound", "hbx_idset_slots",
+               "hbx_restore_in_bound")
 
 
 class FileEntry(ctypes.Structure):
@@ -103,6 +105,15 @@ class SegChunks(ctypes.Structure):
 
 # hbx_seg_sink_fn (include/hbxgpu.h)
 SEG_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SegChunks))
+
+# hbx_block_source_fn / hbx_restore_sink_fn (include/hbxgpu.h)
+BLOCK_SOURCE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8))
+RESTORE_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64)
+BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
+MAX_BLOCK = 8 << 20                 # HBX_MAX_BLOCK
+ERR_IO, ERR_VERIFY = -4, -9
+NO_DIFF = (1 << 64) - 1             # first_diff when nothing differs
 
 _lib = None
 
@@ -224,6 +235,11 @@ def load() -> ctypes.CDLL:
     L.hbx_store_paths_dd.argtypes = L.hbx_store_paths_status.argtypes + [P, P]
     L.hbx_seg_submit_device_dd.argtypes = L.hbx_seg_submit_device.argtypes + [P, P]
     L.hbx_store_file_stream.argtypes = [P, ctypes.c_char_p, U64, U64, ctypes.c_uint32, ctypes.c_uint32, P, P, P, P]
+    L.hbx_restore_in_bound.argtypes = [U64]
+    L.hbx_restore_in_bound.restype = U64
+    L.hbx_restore_blocks.argtypes = [P, U64, P, P, P, P, P, P, P, U64, P, U64, P, U64, P, P, PU64, PU64]
+    L.hbx_restore_file_stream.argtypes = [P, U64, P, P, P, U64, ctypes.c_char_p, P, ctypes.c_char_p, U64, PU64, PU64,
+                                          PU32, PU64]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -40,6 +41,7 @@
 #include "hbx_inflate.hip"
 #include "hbx_inflate_split.hip"
 #include "hbx_dedup.hip"
+#include "hbx_restore.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 
@@ -373,6 +375,15 @@ struct hbx_ctx {
   DevBuf d_zblk, d_zinfo, d_zoff, d_zlen, d_zout, d_zimg;  // hbx_deflate_blocks*
   DevBuf d_idesc, d_ires;                                  // hbx_inflate_blocks_device
   DevBuf d_sreg, d_sstart, d_sres, d_sscratch, d_smeta;    // its split path (K8s)
+  // hbx_restore_*: staged input (two windows), inflate slots, the gathered
+  // image / the local copy (diff), the piece table, the diff word; the pinned
+  // staging and output of two windows; the stream the next window is filled on
+  DevBuf d_rin[2], d_rslots, d_rimg, d_rpiece, d_rword;
+  PinBuf h_rin[2], h_rout[2];
+  hipStream_t fstream = nullptr;
+  // host ms of the latest hbx_restore_* call per phase, each ending on a
+  // synchronization: input staging, inflate, VerifyBlock beside K10, copy-out
+  double restore_ms[4] = {0, 0, 0, 0};
   uint64_t k8_split_streams = 0, k8_split_fallbacks = 0;   // (hbx_knobs: how often the split path resolved)
   // SDMA engines warmed at context creation (warm_sdma_engines): H2D and D2H
   // engine masks, and the milliseconds this context spent on it (0 once the
@@ -1823,8 +1834,14 @@ void hbx_ctx_destroy(hbx_ctx* c) {
                     &c->d_stage, &c->d_msg, &c->d_plan, &c->d_vdesc, &c->d_vlinks,
                     &c->d_vout, &c->d_vexp, &c->d_zeros, &c->d_zblk, &c->d_zinfo, &c->d_zoff,
                     &c->d_zlen, &c->d_zout, &c->d_zimg, &c->d_idesc, &c->d_ires, &c->d_sreg, &c->d_sstart,
-                    &c->d_sres, &c->d_sscratch, &c->d_smeta})
+                    &c->d_sres, &c->d_sscratch, &c->d_smeta, &c->d_rin[0], &c->d_rin[1], &c->d_rslots, &c->d_rimg,
+                    &c->d_rpiece, &c->d_rword})
     b->release();
+  for (PinBuf* h : {&c->h_rin[0], &c->h_rin[1], &c->h_rout[0], &c->h_rout[1]}) h->release();
+  if (c->fstream) {
+    (void)hipStreamSynchronize(c->fstream);
+    (void)hipStreamDestroy(c->fstream);
+  }
   for (PinBuf& h : c->h_read) h.release();
   c->h_zstage.release();
   for (auto& z : c->zs)
@@ -2012,12 +2029,14 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"lean_marks\": %u, \"k3_prod\": %u, \"k3_items\": %u, \"k3_period\": %u, \"meta_kernel\": %u, "
       "\"plan_cut\": %u, \"k1_swz\": %u, \"k3_psets\": %u, \"d2h_kernel\": %u, \"k8_split_streams\": %llu, "
       "\"k8_split_fallbacks\": %llu, \"gate_meta\": %u, \"sdma_warm\": %u, \"sdma_h2d_mask\": %u, "
-      "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u}",
+      "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
+      "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f]}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
       (unsigned long long)c->k8_split_streams, (unsigned long long)c->k8_split_fallbacks, c->gate_meta,
-      c->sdma_warm, c->sdma_h2d, c->sdma_d2h, c->sdma_warm_ms, c->k3_spin, c->plan_addr, c->plan_addr_shift, c->k1_ext, c->k1_dma4, c->k1_early);
+      c->sdma_warm, c->sdma_h2d, c->sdma_d2h, c->sdma_warm_ms, c->k3_spin, c->plan_addr, c->plan_addr_shift, c->k1_ext, c->k1_dma4, c->k1_early,
+      c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3]);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -2514,7 +2533,9 @@ int hbx_md5(hbx_ctx* c, const uint8_t* data, uint64_t len, uint8_t out[16]) {
 namespace {
 // K6 over n blocks whose data is already on the device (block i at
 // arena + offs[i]); lanes are ordered longest first so each wave's 64 chains
-// are about equally long.
+// are about equally long.  The restore path passes arena = NULL with absolute
+// device addresses in offs (its blocks lie in two buffers): the sum is only
+// ever turned into an integer address, so that is part of this contract.
 int verify_device(hbx_ctx* c, const uint8_t* arena, uint64_t n, const uint64_t* offs,
                   const uint64_t* lens, const uint8_t* links, const uint64_t* link_base,
                   const uint32_t* n_links, uint8_t* ids, const uint8_t* expect, uint8_t* ok,
@@ -2543,7 +2564,7 @@ int verify_device(hbx_ctx* c, const uint8_t* arena, uint64_t n, const uint64_t* 
   for (uint64_t k = 0; k < n; k++) {
     const uint32_t i = perm[k];
     const uint32_t nl = n_links ? n_links[i] : 0u;
-    desc[k].src = reinterpret_cast<uint64_t>(arena + offs[i]);
+    desc[k].src = reinterpret_cast<uint64_t>(arena) + offs[i];
     desc[k].links = reinterpret_cast<uint64_t>(dl + (nl ? 16 * link_base[i] : 0));
     desc[k].len = (uint32_t)lens[i];
     desc[k].n_links = nl;
@@ -4017,14 +4038,21 @@ int hbx_verify_submit_device(hbx_ctx* c, const void* d_arena, uint64_t n, const 
 }
 
 // ---- zlib inflate (hbx_inflate.hip) -----------------------------------------
-int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const uint64_t* in_offs,
-                              const uint64_t* in_lens, void* d_out, const uint64_t* out_offs,
-                              const uint64_t* out_caps, uint64_t* out_lens, uint32_t* status) {
-  if (!c || (n && (!d_in || !in_offs || !in_lens || !d_out || !out_offs || !out_caps || !out_lens || !status)))
-    return HBX_ERR_ARG;
-  std::lock_guard<std::mutex> g(c->mu);
-  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+// K8 / K8s over n streams (the context locked, nothing pending): what
+// hbx_inflate_blocks_device and the restore path (hbx_restore_*) share.
+// out_hint (NULL: out_caps) is what the choice of kernel and the split path's
+// scratch are sized by: the restore path knows no stream's inflated size, so
+// its capacities are all max_block and say nothing; it passes an estimate from
+// the compressed length instead.  A stream that outgrows the estimate is
+// inflated again by the wave kernel, as any split overflow is; the bounds every
+// kernel checks are out_caps.  d_in (and d_out) may be NULL with absolute
+// device addresses in in_offs (out_offs): only their integer sum is used.
+static int inflate_device(hbx_ctx* c, const void* d_in, uint64_t n, const uint64_t* in_offs,
+                          const uint64_t* in_lens, void* d_out, const uint64_t* out_offs,
+                          const uint64_t* out_caps, uint64_t* out_lens, uint32_t* status,
+                          const uint64_t* out_hint = nullptr) {
   if (n == 0) return HBX_OK;
+  if (!out_hint) out_hint = out_caps;
   if (n > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "too many streams");
   HBX_TRY(c, hipSetDevice(c->device));
   // one wave per stream, longest first (the long ones start first)
@@ -4043,7 +4071,7 @@ int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const ui
   uint64_t tin = 0, tcap = 0;
   for (uint64_t i = 0; i < n; i++) {
     tin += in_lens[i];
-    tcap += out_caps[i];
+    tcap += out_hint[i];
   }
   bool lanes = n >= 8192 && tin * 10 < tcap * 7 && tcap / n <= (256u << 10);
   const char* mode = ab_env("HBX_K8_MODE");
@@ -4052,7 +4080,7 @@ int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const ui
   const bool no_split = lanes || (mode && std::strcmp(mode, "wave") == 0);
   auto splits = [&](uint32_t i) {
     if (no_split || in_lens[i] < 2ull * hbxs::kSplitRegion) return false;
-    return force_split || in_lens[i] * 10 < out_caps[i] * 8;
+    return force_split || in_lens[i] * 10 < out_hint[i] * 8;
   };
   // Scratch of one split stream: regions of kSplitRegion compressed bytes,
   // each with room for twice its share of the stream's output capacity in
@@ -4083,7 +4111,7 @@ int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const ui
       const uint32_t i = perm[k];
       if (!splits(i)) continue;
       uint32_t cnt = 0;
-      const uint64_t syms = region_syms(in_lens[i], out_caps[i], cnt);
+      const uint64_t syms = region_syms(in_lens[i], out_hint[i], cnt);
       const uint64_t b = 2ull * syms * cnt;  // scratch bytes of its regions
       if (used + b > budget) continue;
       used += b;
@@ -4117,7 +4145,7 @@ int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const ui
     uint64_t sym = 0;
     for (uint64_t k = nw; k < n; k++) {
       uint32_t cnt = 0;
-      const uint32_t scap = (uint32_t)region_syms(desc[k].len, desc[k].cap, cnt);
+      const uint32_t scap = (uint32_t)region_syms(desc[k].len, out_hint[perm[k]], cnt);
       meta[k - nw] = (uint32_t)k;
       meta[(n - nw) + (k - nw)] = (uint32_t)reg.size();
       meta[2 * (n - nw) + (k - nw)] = cnt;
@@ -4202,6 +4230,533 @@ int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const ui
   // is idle here: everything above was synchronized)
   if (c->d_sscratch.cap > (256ull << 20)) c->d_sscratch.release();
   return HBX_OK;
+}
+
+int hbx_inflate_blocks_device(hbx_ctx* c, const void* d_in, uint64_t n, const uint64_t* in_offs,
+                              const uint64_t* in_lens, void* d_out, const uint64_t* out_offs,
+                              const uint64_t* out_caps, uint64_t* out_lens, uint32_t* status) {
+  if (!c || (n && (!d_in || !in_offs || !in_lens || !d_out || !out_offs || !out_caps || !out_lens || !status)))
+    return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  return inflate_device(c, d_in, n, in_offs, in_lens, d_out, out_offs, out_caps, out_lens, status);
+}
+
+}  // extern "C"
+
+// ---- restore and diff (hbx_restore.hip, K10) ----------------------------------
+namespace {
+
+constexpr uint64_t kRestoreMaxBlock = 1ull << 30;  // largest max_block accepted (lengths stay well inside 32 bits)
+
+inline uint64_t restore_mb(uint64_t max_block) { return max_block ? max_block : (uint64_t)HBX_MAX_BLOCK; }
+// One inflate slot: the block's capacity, K6's read slack, a multiple of 256.
+inline uint64_t restore_stride(uint64_t mb) { return (mb + 256ull + 255ull) & ~255ull; }
+
+// One window of a block chain, its data fields already in device memory.
+struct RestoreWin {
+  uint64_t n = 0;
+  const uint64_t* src = nullptr;   // device address of block i's data field
+  const uint64_t* lens = nullptr;  // its length
+  const uint8_t* types = nullptr;  // HBX_BLOCK_RAW / HBX_BLOCK_ZLIB
+  const uint8_t* expect = nullptr; // 16 n: the expected BlockIDs
+  const uint8_t* links = nullptr;  // as hbx_verify_blocks (may all be NULL)
+  const uint64_t* link_base = nullptr;
+  const uint32_t* n_links = nullptr;
+  uint64_t max_block = HBX_MAX_BLOCK;
+  uint64_t* offs = nullptr;     // out, n + 1: byte offsets in the window, valid up to offs[n_good]
+  uint32_t* status = nullptr;   // in: 0, or 8 from the caller's pre-check; out: the block's status
+  uint64_t n_good = 0;          // out: leading blocks with status 0
+  uint64_t first_diff = hbxr::kNoDiff;  // out (diff): smallest differing offset inside the good prefix
+};
+
+// What the window's blocks are put into: a contiguous image (device or pinned
+// host memory, `cap` bytes), or compared with: `local(total, &d, &avail)` must
+// leave the local copy's bytes [0, avail) of this window at device address d
+// on the result stream (avail <= total).  Neither: the blocks are only
+// inflated and verified (the rest of a chain after its first bad block).
+using RestoreLocalFn = std::function<int(uint64_t, const uint8_t**, uint64_t*)>;
+
+// The image is the engine's own buffer and starts kImageLead bytes into it:
+// the kImageGuard bytes before image[0] and after image[total) hold a pattern
+// while K10 runs and are checked after it, so a gather that wrote outside
+// [0, total) fails the call instead of passing unseen (the caller's buffer is
+// filled by a copy of exactly the good prefix and could never show it).
+constexpr uint64_t kImageLead = 256, kImageGuard = 64;
+constexpr uint8_t kGuardByte = 0xC3;
+
+// Inflate (K8 / K8s, on the scan stream), then VerifyBlock (K6, scan stream)
+// beside the gather or diff (K10, result stream): both read the slots, neither
+// waits for the other.  K10 covers the blocks that inflated; the caller keeps
+// what lies before offs[n_good].  Synchronous: every stream it used is idle on
+// return, also on failure.
+int restore_window(hbx_ctx* c, RestoreWin& w, uint8_t* image, uint64_t cap, bool image_on_host,
+                   const RestoreLocalFn* local) {
+  const uint64_t n = w.n;
+  w.n_good = 0;
+  w.first_diff = hbxr::kNoDiff;
+  w.offs[0] = 0;
+  if (n == 0) return HBX_OK;
+  const uint64_t stride = restore_stride(w.max_block);
+  HBX_TRY(c, c->d_rword.ensure(4096));
+  // 1. inflate the zlib blocks into their slots; the lengths come back to the host
+  std::vector<uint64_t> zi, in_offs, in_lens, out_offs, out_caps, out_hint, out_lens;
+  std::vector<uint32_t> zst;
+  for (uint64_t i = 0; i < n; i++)
+    if (w.status[i] == 0 && w.types[i] == HBX_BLOCK_ZLIB) {
+      zi.push_back(i);
+      in_offs.push_back(w.src[i]);
+      in_lens.push_back(w.lens[i]);
+      out_offs.push_back((zi.size() - 1) * stride);
+      out_caps.push_back(w.max_block);
+      // (text compresses 3:1 to 4:1; the split path leaves room for twice the hint)
+      out_hint.push_back(std::min<uint64_t>(w.max_block, 8 * w.lens[i] + 4096));
+    }
+  const uint64_t nz = zi.size();
+  const auto t_inflate = std::chrono::steady_clock::now();
+  out_lens.assign(nz, 0);
+  zst.assign(nz, 0);
+  if (nz) {
+    HBX_TRY(c, c->d_rslots.ensure(nz * stride + 65536));
+    if (int rc = inflate_device(c, nullptr, nz, in_offs.data(), in_lens.data(), c->d_rslots.p, out_offs.data(),
+                                out_caps.data(), out_lens.data(), zst.data(), out_hint.data()))
+      return rc;
+  }
+  c->restore_ms[1] += ms_since(t_inflate);
+  const auto t_verify = std::chrono::steady_clock::now();
+  std::vector<uint64_t> addr(n), dlen(n);
+  const uint64_t nowhere = reinterpret_cast<uint64_t>(c->d_rword.p);
+  for (uint64_t i = 0; i < n; i++) {
+    addr[i] = nowhere;
+    dlen[i] = 0;
+    if (w.status[i] == 0 && w.types[i] == HBX_BLOCK_RAW) {
+      if (w.lens[i] > w.max_block) {
+        w.status[i] = hbxi::kErrOutput;
+      } else {
+        addr[i] = w.src[i];
+        dlen[i] = w.lens[i];
+      }
+    }
+  }
+  for (uint64_t k = 0; k < nz; k++) {
+    const uint64_t i = zi[k];
+    w.status[i] = zst[k];
+    if (zst[k] == 0) {
+      addr[i] = reinterpret_cast<uint64_t>(c->d_rslots.p) + out_offs[k];
+      dlen[i] = out_lens[k];
+    }
+  }
+  // 2. the prefix sum over the blocks that may still be good, and their pieces
+  uint64_t m = 0;
+  while (m < n && w.status[m] == 0) {
+    w.offs[m + 1] = w.offs[m] + dlen[m];
+    m++;
+  }
+  const uint64_t total = w.offs[m];
+  hipStream_t rs = c->rstream;
+  const uint8_t* d_local = nullptr;
+  uint64_t avail = 0;
+  const bool diff = local != nullptr && *local;
+  if (diff) {
+    if (int rc = (*local)(total, &d_local, &avail)) return rc;
+    avail = std::min(avail, total);
+  } else if (image && total > cap) {
+    return c->fail(HBX_ERR_CAPACITY, "restore: the window's image is too small");
+  }
+  const uint64_t cover = diff ? avail : (image ? total : 0);  // bytes K10 touches
+  std::vector<hbxr::Piece> pieces;
+  for (uint64_t i = 0; i < m && w.offs[i] < cover; i++) {
+    const uint64_t len = std::min(dlen[i], cover - w.offs[i]);
+    for (uint64_t p = 0; p < len; p += hbxr::kPiece)
+      pieces.push_back(hbxr::Piece{addr[i] + p, w.offs[i] + p, (uint32_t)std::min<uint64_t>(hbxr::kPiece, len - p), 0u});
+  }
+  if (pieces.size() > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "restore: window too large");
+  uint64_t word = hbxr::kNoDiff;
+  uint8_t guard[2 * kImageGuard];
+  std::memset(guard, kGuardByte, sizeof guard);
+  const bool guarded = !diff && image && !pieces.empty();
+  int krc = HBX_OK;
+  if (!pieces.empty()) {
+    krc = [&]() -> int {
+      HBX_TRY(c, c->d_rpiece.ensure(pieces.size() * sizeof(hbxr::Piece)));
+      HBX_TRY(c, hipMemcpyAsync(c->d_rpiece.p, pieces.data(), pieces.size() * sizeof(hbxr::Piece),
+                                hipMemcpyHostToDevice, rs));
+      if (diff) {
+        HBX_TRY(c, hipMemsetAsync(c->d_rword.p, 0xFF, 8, rs));
+        hipLaunchKernelGGL(hbx_k10_diff, dim3((uint32_t)pieces.size()), dim3(hbxr::kThreads), 0, rs,
+                           c->d_rpiece.as<hbxr::Piece>(), (uint32_t)pieces.size(), d_local,
+                           c->d_rword.as<unsigned long long>());
+        HBX_TRY(c, hipGetLastError());
+        HBX_TRY(c, hipMemcpyAsync(&word, c->d_rword.p, 8, hipMemcpyDeviceToHost, rs));
+      } else {
+        if (image_on_host) {
+          std::memset(image - kImageGuard, kGuardByte, kImageGuard);
+          std::memset(image + total, kGuardByte, kImageGuard);
+        } else {
+          HBX_TRY(c, hipMemsetAsync(image - kImageGuard, kGuardByte, kImageGuard, rs));
+          HBX_TRY(c, hipMemsetAsync(image + total, kGuardByte, kImageGuard, rs));
+        }
+        hipLaunchKernelGGL(hbx_k10_gather, dim3((uint32_t)pieces.size()), dim3(hbxr::kThreads), 0, rs,
+                           c->d_rpiece.as<hbxr::Piece>(), (uint32_t)pieces.size(), image);
+        HBX_TRY(c, hipGetLastError());
+        if (!image_on_host) {
+          HBX_TRY(c, hipMemcpyAsync(guard, image - kImageGuard, kImageGuard, hipMemcpyDeviceToHost, rs));
+          HBX_TRY(c, hipMemcpyAsync(guard + kImageGuard, image + total, kImageGuard, hipMemcpyDeviceToHost, rs));
+        }
+      }
+      return HBX_OK;
+    }();
+  }
+  // 3. VerifyBlock of every block that inflated, links passed through
+  std::vector<uint32_t> nl(n, 0u);
+  if (w.n_links)
+    for (uint64_t i = 0; i < n; i++)
+      if (w.status[i] == 0) nl[i] = w.n_links[i];
+  std::vector<uint8_t> ok(n, 0);
+  int vrc = krc ? HBX_OK
+                : verify_device(c, nullptr, n, addr.data(), dlen.data(), w.links, w.link_base, nl.data(), nullptr,
+                                w.expect, ok.data(), nullptr);
+  const std::string verr = c->err;
+  const int src_ = c->hip(hipStreamSynchronize(rs), "hipStreamSynchronize(result stream)");
+  c->restore_ms[2] += ms_since(t_verify);
+  if (krc) return krc;
+  if (vrc) return c->fail(vrc, verr);
+  if (src_) return src_;
+  if (guarded) {
+    if (image_on_host) {
+      std::memcpy(guard, image - kImageGuard, kImageGuard);
+      std::memcpy(guard + kImageGuard, image + total, kImageGuard);
+    }
+    for (uint8_t b : guard)
+      if (b != kGuardByte) return c->fail(HBX_ERR_STATE, "restore: K10 wrote outside the image");
+  }
+  for (uint64_t i = 0; i < n; i++)
+    if (w.status[i] == 0 && !ok[i]) w.status[i] = 7;
+  while (w.n_good < n && w.status[w.n_good] == 0) w.n_good++;
+  if (word < w.offs[w.n_good]) w.first_diff = word;
+  return HBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t hbx_restore_in_bound(uint64_t max_block) {
+  const uint64_t mb = restore_mb(max_block);
+  return hbx_deflate_bound(mb) + 64;
+}
+
+int hbx_restore_blocks(hbx_ctx* c, uint64_t n, const uint8_t* const* datas, const uint64_t* lens,
+                       const uint8_t* types, const uint8_t* expect, const uint8_t* links,
+                       const uint64_t* link_base, const uint32_t* n_links, uint64_t max_block, uint8_t* out,
+                       uint64_t out_cap, const uint8_t* local, uint64_t local_len, uint64_t* offs,
+                       uint32_t* status, uint64_t* n_good, uint64_t* first_diff) {
+  if (!c || !offs || !n_good || (n && (!datas || !lens || !types || !expect || !status))) return HBX_ERR_ARG;
+  if ((out != nullptr) == (local != nullptr)) return HBX_ERR_ARG;  // exactly one target
+  if (local && !first_diff) return HBX_ERR_ARG;
+  const uint64_t mb = restore_mb(max_block);
+  if (mb > kRestoreMaxBlock || n > 0x7FFFFFFFull) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  const uint64_t bound = hbx_restore_in_bound(mb), stride = restore_stride(mb);
+  for (double& t : c->restore_ms) t = 0.0;
+  offs[0] = 0;
+  *n_good = 0;
+  if (first_diff) *first_diff = hbxr::kNoDiff;
+  for (uint64_t i = 0; i < n; i++) {
+    const bool known = types[i] == HBX_BLOCK_RAW || types[i] == HBX_BLOCK_ZLIB;
+    status[i] = (!known || lens[i] > bound) ? 8u : 0u;
+    if (status[i] == 0 && lens[i] && !datas[i]) return c->fail(HBX_ERR_ARG, "null block data");
+  }
+  // Windows of as many blocks as a slot budget holds (a quarter of the free
+  // device memory, at most 64 GiB): every zlib block needs a slot of max_block.
+  size_t fr = 0, tot = 0;
+  uint64_t budget = 1ull << 30;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::max<uint64_t>(budget, std::min<uint64_t>(fr / 4, 64ull << 30));
+  const uint64_t per = std::max<uint64_t>(1, budget / stride);
+  bool stopped = false;  // a bad block was met: the rest is only inflated and verified, for its status
+  uint64_t found = hbxr::kNoDiff;
+  std::vector<uint64_t> src, woffs;
+  for (uint64_t a = 0; a < n; a += per) {
+    const uint64_t b = std::min(n, a + per), wn = b - a;
+    // stage the data fields: zlib streams at 16-byte boundaries (K8's vector
+    // loads), raw blocks packed byte by byte behind whatever precedes them
+    const auto t_stage = std::chrono::steady_clock::now();
+    src.assign(wn, 0);
+    uint64_t pos = 0;
+    for (uint64_t i = a; i < b; i++) {
+      if (status[i]) continue;
+      if (types[i] == HBX_BLOCK_ZLIB) pos = (pos + 15) & ~15ull;
+      src[i - a] = pos;
+      pos += lens[i];
+    }
+    HBX_TRY(c, c->d_rin[0].ensure(pos + 65536));
+    uint8_t* din = c->d_rin[0].as<uint8_t>();
+    for (uint64_t i = a; i < b; i++) {
+      if (status[i] == 0 && lens[i])
+        HBX_TRY(c, hipMemcpyAsync(din + src[i - a], datas[i], lens[i], hipMemcpyHostToDevice, c->stream));
+      src[i - a] += reinterpret_cast<uint64_t>(din);
+    }
+    HBX_TRY(c, hipStreamSynchronize(c->stream));
+    c->restore_ms[0] += ms_since(t_stage);
+    RestoreWin w;
+    w.n = wn;
+    w.src = src.data();
+    w.lens = lens + a;
+    w.types = types + a;
+    w.expect = expect + 16 * a;
+    w.links = links;
+    w.link_base = link_base ? link_base + a : nullptr;
+    w.n_links = n_links ? n_links + a : nullptr;
+    w.max_block = mb;
+    woffs.assign(wn + 1, 0);
+    w.offs = woffs.data();
+    w.status = status + a;
+    const uint64_t base = offs[a];
+    uint8_t* image = nullptr;
+    uint64_t cap = 0;
+    if (!stopped && out) {  // (the image's size is known only after the inflate: the window's upper bound)
+      uint64_t ub = 0;
+      for (uint64_t i = a; i < b; i++) ub += status[i] ? 0 : (types[i] == HBX_BLOCK_RAW ? lens[i] : mb);
+      cap = std::min<uint64_t>(ub, wn * mb);
+      HBX_TRY(c, c->d_rimg.ensure(kImageLead + cap + kImageGuard));
+      image = c->d_rimg.as<uint8_t>() + kImageLead;
+    }
+    RestoreLocalFn lf;
+    if (!stopped && local)
+      lf = [&](uint64_t total, const uint8_t** d, uint64_t* avail) -> int {
+        const uint64_t have = local_len > base ? std::min(total, local_len - base) : 0;
+        HBX_TRY(c, c->d_rimg.ensure(have + 256));
+        if (have) HBX_TRY(c, hipMemcpyAsync(c->d_rimg.p, local + base, have, hipMemcpyHostToDevice, c->rstream));
+        *d = c->d_rimg.as<uint8_t>();
+        *avail = have;
+        return HBX_OK;
+      };
+    if (int rc = restore_window(c, w, image, cap, false, &lf)) return rc;
+    if (stopped) continue;
+    for (uint64_t i = 0; i < w.n_good; i++) offs[a + i + 1] = base + woffs[i + 1];
+    *n_good = a + w.n_good;
+    const uint64_t good = woffs[w.n_good];
+    if (out && good) {
+      if (base + good > out_cap) return c->fail(HBX_ERR_ARG, "out_cap is smaller than the restored prefix");
+      const auto t_out = std::chrono::steady_clock::now();
+      HBX_TRY(c, hipMemcpy(out + base, image, good, hipMemcpyDeviceToHost));
+      c->restore_ms[3] += ms_since(t_out);
+    }
+    if (w.first_diff != hbxr::kNoDiff && found == hbxr::kNoDiff) found = base + w.first_diff;
+    if (w.n_good < wn) stopped = true;
+  }
+  if (local) {
+    const uint64_t total = offs[*n_good];
+    *first_diff = found != hbxr::kNoDiff ? found : local_len != total ? std::min(local_len, total) : hbxr::kNoDiff;
+  }
+  return HBX_OK;
+}
+
+int hbx_restore_file_stream(hbx_ctx* c, uint64_t n_blocks, const uint8_t* ids, hbx_block_source_fn source,
+                            void* user, uint64_t window_bytes, const char* out_path, hbx_restore_sink_fn sink,
+                            const char* local_path, uint64_t max_block, uint64_t* bytes, uint64_t* bad_index,
+                            uint32_t* bad_status, uint64_t* first_diff) {
+  if (!c || (n_blocks && (!ids || !source))) return HBX_ERR_ARG;
+  if ((out_path ? 1 : 0) + (sink ? 1 : 0) + (local_path ? 1 : 0) != 1) return HBX_ERR_ARG;  // exactly one target
+  if (local_path && !first_diff) return HBX_ERR_ARG;
+  const uint64_t mb = restore_mb(max_block);
+  if (mb > kRestoreMaxBlock) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  for (double& t : c->restore_ms) t = 0.0;
+  if (bytes) *bytes = 0;
+  if (bad_index) *bad_index = ~0ull;
+  if (bad_status) *bad_status = 0;
+  if (first_diff) *first_diff = hbxr::kNoDiff;
+  const uint64_t bound = hbx_restore_in_bound(mb), stride = restore_stride(mb);
+  if (window_bytes == 0) window_bytes = 1ull << 30;
+  const uint64_t per = std::min<uint64_t>(std::max<uint64_t>(1, window_bytes / stride), std::max<uint64_t>(n_blocks, 1));
+  const uint64_t in_slot = ((bound + 15) & ~15ull);
+  // every buffer is sized by the window, never by the chain
+  for (int k = 0; k < 2; k++) {
+    HBX_TRY(c, c->h_rin[k].ensure(per * in_slot + 64));
+    HBX_TRY(c, c->d_rin[k].ensure(per * in_slot + 65536));
+    HBX_TRY(c, c->h_rout[k].ensure(kImageLead + per * mb + kImageGuard));
+  }
+  HBX_TRY(c, c->d_rslots.ensure(per * stride + 65536));
+  if (local_path) HBX_TRY(c, c->d_rimg.ensure(per * mb + 256));
+  if (!c->fstream) HBX_TRY(c, hipStreamCreateWithFlags(&c->fstream, hipStreamNonBlocking));
+  int fd = -1;
+  uint64_t local_len = 0;
+  if (out_path) {
+    fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+    if (fd < 0) return c->fail(HBX_ERR_IO, std::string("cannot create ") + out_path + ": " + std::strerror(errno));
+  } else if (local_path) {
+    fd = ::open(local_path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return c->fail(HBX_ERR_IO, std::string("cannot open ") + local_path + ": " + std::strerror(errno));
+    const off_t end = ::lseek(fd, 0, SEEK_END);
+    if (end < 0) {
+      ::close(fd);
+      return c->fail(HBX_ERR_IO, std::string("cannot size ") + local_path);
+    }
+    local_len = (uint64_t)end;
+  }
+  struct Filled {  // one window's staged input
+    uint64_t first = 0, n = 0;
+    std::vector<uint64_t> src, lens;
+    std::vector<uint8_t> types;
+    std::vector<uint32_t> status;
+    std::string err;
+  };
+  Filled fill[2];
+  const uint64_t nwin = (n_blocks + per - 1) / per;
+  // the source fills window k's pinned staging and the copy to the device runs
+  // on a stream of its own, while the previous window inflates
+  auto do_fill = [&](uint64_t k) -> int {
+    Filled& f = fill[k & 1];
+    f.first = k * per;
+    f.n = std::min(per, n_blocks - f.first);
+    f.src.assign(f.n, 0);
+    f.lens.assign(f.n, 0);
+    f.types.assign(f.n, 0);
+    f.status.assign(f.n, 0);
+    f.err.clear();
+    if (hipSetDevice(c->device) != hipSuccess) {
+      f.err = "hipSetDevice failed on the fill thread";
+      return HBX_ERR_HIP;
+    }
+    uint8_t* h = c->h_rin[k & 1].as<uint8_t>();
+    uint8_t* d = c->d_rin[k & 1].as<uint8_t>();
+    uint64_t pos = 0;
+    for (uint64_t i = 0; i < f.n; i++) {
+      pos = (pos + 15) & ~15ull;
+      uint64_t len = 0;
+      uint8_t type = 0;
+      if (source(user, f.first + i, h + pos, bound, &len, &type) != 0) {
+        f.err = "the block source failed at block " + std::to_string(f.first + i);
+        return HBX_ERR_IO;
+      }
+      f.types[i] = type;
+      f.src[i] = reinterpret_cast<uint64_t>(d) + pos;
+      if (len > bound || (type != HBX_BLOCK_RAW && type != HBX_BLOCK_ZLIB)) {
+        f.status[i] = 8;
+        continue;
+      }
+      f.lens[i] = len;
+      pos += len;
+    }
+    hipError_t e = pos ? hipMemcpyAsync(d, h, pos, hipMemcpyHostToDevice, c->fstream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->fstream);
+    if (e != hipSuccess) {
+      f.err = std::string("restore input copy: ") + hipGetErrorString(e);
+      return HBX_ERR_HIP;
+    }
+    return HBX_OK;
+  };
+  // window k's good prefix, gathered into pinned memory, to the file or the sink
+  std::string out_err;
+  auto do_out = [&](int slot, uint64_t file_off, uint64_t len) -> int {
+    const uint8_t* p = c->h_rout[slot].as<uint8_t>() + kImageLead;
+    if (sink) {
+      if (len && sink(user, file_off, p, len) != 0) {
+        out_err = "the restore sink failed at offset " + std::to_string(file_off);
+        return HBX_ERR_IO;
+      }
+      return HBX_OK;
+    }
+    for (uint64_t done = 0; done < len;) {
+      const ssize_t r = ::pwrite(fd, p + done, len - done, (off_t)(file_off + done));
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) {
+        out_err = std::string("cannot write ") + out_path + ": " + std::strerror(errno);
+        return HBX_ERR_IO;
+      }
+      done += (uint64_t)r;
+    }
+    return HBX_OK;
+  };
+  int rc = HBX_OK;
+  uint64_t file_off = 0;
+  std::future<int> filling, writing;
+  std::vector<uint64_t> woffs;
+  if (nwin) filling = std::async(std::launch::async, do_fill, (uint64_t)0);
+  for (uint64_t k = 0; k < nwin && rc == HBX_OK; k++) {
+    rc = filling.get();
+    Filled& f = fill[k & 1];
+    if (rc) {
+      c->err = f.err;
+      break;
+    }
+    if (k + 1 < nwin) filling = std::async(std::launch::async, do_fill, k + 1);
+    RestoreWin w;
+    w.n = f.n;
+    w.src = f.src.data();
+    w.lens = f.lens.data();
+    w.types = f.types.data();
+    w.expect = ids + 16 * f.first;
+    w.max_block = mb;
+    woffs.assign(f.n + 1, 0);
+    w.offs = woffs.data();
+    w.status = f.status.data();
+    RestoreLocalFn lf;
+    if (local_path)
+      lf = [&](uint64_t total, const uint8_t** d, uint64_t* avail) -> int {
+        const uint64_t have = local_len > file_off ? std::min(total, local_len - file_off) : 0;
+        uint8_t* h = c->h_rout[k & 1].as<uint8_t>();
+        for (uint64_t done = 0; done < have;) {
+          const ssize_t r = ::pread(fd, h + done, have - done, (off_t)(file_off + done));
+          if (r < 0 && errno == EINTR) continue;
+          if (r <= 0) return c->fail(HBX_ERR_IO, std::string("short read of ") + local_path);
+          done += (uint64_t)r;
+        }
+        if (have) HBX_TRY(c, hipMemcpyAsync(c->d_rimg.p, h, have, hipMemcpyHostToDevice, c->rstream));
+        *d = c->d_rimg.as<uint8_t>();
+        *avail = have;
+        return HBX_OK;
+      };
+    // (the pinned output slot k & 1 is free: window k - 2's write was joined
+    // before window k - 1's began)
+    rc = restore_window(c, w, local_path ? nullptr : c->h_rout[k & 1].as<uint8_t>() + kImageLead, f.n * mb, true,
+                        &lf);
+    if (rc) break;
+    const uint64_t good = woffs[w.n_good];
+    if (writing.valid()) {
+      rc = writing.get();
+      if (rc) {
+        c->err = out_err;
+        break;
+      }
+    }
+    if (!local_path) writing = std::async(std::launch::async, do_out, (int)(k & 1), file_off, good);
+    if (local_path && w.first_diff != hbxr::kNoDiff) {  // the first event in chain order is a difference
+      *first_diff = file_off + w.first_diff;
+      file_off += good;
+      break;
+    }
+    file_off += good;
+    if (w.n_good < f.n) {
+      if (bad_index) *bad_index = f.first + w.n_good;
+      if (bad_status) *bad_status = f.status[w.n_good];
+      rc = c->fail(HBX_ERR_VERIFY, "block " + std::to_string(f.first + w.n_good) + " failed with status " +
+                                       std::to_string(f.status[w.n_good]));
+      break;
+    }
+    if (local_path && file_off > local_len) {  // the local copy ended inside this window
+      *first_diff = local_len;
+      break;
+    }
+  }
+  // drain: nothing of this call stays in flight, whatever happened
+  if (filling.valid()) (void)filling.get();
+  if (writing.valid()) {
+    const int wrc = writing.get();
+    if (wrc && rc == HBX_OK) rc = c->fail(wrc, out_err);
+  }
+  for (hipStream_t s : {c->stream, c->rstream, c->fstream}) (void)hipStreamSynchronize(s);
+  if (fd >= 0 && ::close(fd) != 0 && out_path && rc == HBX_OK)
+    rc = c->fail(HBX_ERR_IO, std::string("cannot close ") + out_path);
+  if (bytes) *bytes = file_off;
+  if (rc == HBX_OK && local_path && *first_diff == hbxr::kNoDiff && local_len != file_off)
+    *first_diff = std::min(local_len, file_off);
+  return rc;
 }
 
 }  // extern "C"

@@ -46,6 +46,27 @@ class HbxError(RuntimeError):
     """A non-zero status from libhbxgpu."""
 
 
+class RestoreError(HbxError):
+    """:meth:`Engine.restore_file` / :meth:`Engine.diff_file` failed: ``code``
+    is the library's status (``_lib.ERR_VERIFY`` for a bad block, with its
+    ``bad_index`` and ``bad_status``; ``_lib.ERR_IO`` for a failing source,
+    sink, write or local read); ``bytes`` is what was restored before it."""
+
+    def __init__(self, msg: str, code: int, bad_index: Optional[int], bad_status: int, nbytes: int):
+        super().__init__(msg)
+        self.code, self.bad_index, self.bad_status, self.bytes = code, bad_index, bad_status, nbytes
+
+
+@dataclass(slots=True)
+class RestoredBlocks:
+    """What :meth:`Engine.restore_blocks` returns (hbx_restore_blocks)."""
+    data: Optional[bytes]  # the file's bytes up to the first bad block; None in diff mode
+    offs: np.ndarray  # uint64 [n_good + 1]: where each good block starts; offs[-1] = bytes restored
+    status: np.ndarray  # uint32 [n]: 0 ok, 1-6 inflate, 7 ID mismatch, 8 field too long / unknown type
+    n_good: int  # leading blocks with status 0
+    first_diff: Optional[int]  # diff mode: first differing offset, None when nothing differs
+
+
 def max_chunks(n: int) -> int:
     return n // MIN_BLOCK_SIZE + 1
 
@@ -694,6 +715,134 @@ class Engine:
         ol, st = self.inflate_blocks_device(d_in.data_ptr(), io, [a.size for a in arrs], d_out.data_ptr(), oo, oc)
         out = d_out.cpu().numpy()
         return [out[int(oo[i]):int(oo[i] + ol[i])].tobytes() if st[i] == 0 else None for i in range(n)], st
+
+    # ------------------------------------------------------ restore / diff --
+    def restore_blocks(self, datas: Sequence[BytesLike], types: Sequence[int], ids,
+                       links: Optional[Sequence[Sequence[bytes]]] = None, local: Optional[BytesLike] = None,
+                       max_block: Optional[int] = None, out: Optional[np.ndarray] = None) -> RestoredBlocks:
+        """restoreFileData / diffFileData over the blocks of one chain, in file
+        order (hashback/restore.go:45-66, 249-277; hbx_restore_blocks): block i
+        has the data field ``datas[i]`` as read off the wire, the DataType
+        ``types[i]`` (0xff raw, 0x01 zlib) and must hash, with ``links[i]``, to
+        ``ids[i]``.  Every block is inflated and verified on the device as
+        VerifyBlock does; the result covers the blocks before the first bad
+        one.  With ``local`` (the local copy's bytes) nothing is assembled and
+        ``first_diff`` is the first offset at which the two differ.  ``out``
+        (a uint8 array) receives the bytes instead of a fresh buffer."""
+        arrs = [_u8(d) for d in datas]
+        n = len(arrs)
+        ida = _ids_array(ids)
+        if ida.shape[0] != n or len(types) != n:
+            raise ValueError("one type and one 16-byte ID per block")
+        mb = int(max_block) if max_block else _lib.MAX_BLOCK
+        lens = np.array([a.size for a in arrs], np.uint64)
+        ty = np.ascontiguousarray(types, np.uint8)
+        ptrs = np.array([_p(a) for a in arrs], np.uint64)
+        links_a, base, counts = self._links_arrays(links, n)
+        offs = np.zeros(n + 1, np.uint64)
+        status = np.zeros(max(n, 1), np.uint32)
+        n_good, first = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        loc = None
+        if local is not None:
+            if out is not None:
+                raise ValueError("out and local exclude each other")
+            loc = _u8(local)
+            if loc.size == 0:  # (a NULL pointer would mean "no local copy")
+                loc = np.zeros(1, np.uint8)[:0]
+            out_p, out_cap = None, 0
+            loc_p = ctypes.c_void_p(loc.ctypes.data)
+        else:
+            if out is None:  # an upper bound: deflate expands at most 1032-fold
+                cap = sum(int(k) if t == _lib.BLOCK_RAW else min(mb, 1032 * int(k) + 64)
+                          for k, t in zip(lens.tolist(), ty.tolist()))
+                out = np.empty(max(cap, 1), np.uint8)
+            out_p, out_cap, loc_p = ctypes.c_void_p(out.ctypes.data), int(out.size), None
+        self._check(self._L.hbx_restore_blocks(
+            self._ctx, n, _p(ptrs), _p(lens), _p(ty), _p(ida),
+            _p(links_a) if links_a is not None else None, _p(base) if base is not None else None,
+            _p(counts) if counts is not None else None, int(max_block or 0), out_p, out_cap,
+            loc_p, int(loc.size) if loc is not None else 0, _p(offs), _p(status), ctypes.byref(n_good),
+            ctypes.byref(first)), "hbx_restore_blocks")
+        g = int(n_good.value)
+        data = out[:int(offs[g])].tobytes() if loc is None else None
+        fd = None if loc is None or first.value == _lib.NO_DIFF else int(first.value)
+        return RestoredBlocks(data, offs[:g + 1].copy(), status[:n].copy(), g, fd)
+
+    def _restore_stream(self, ids, source, out_path, on_data, local_path, window_bytes: int, max_block):
+        ida = _ids_array(ids)
+        n = int(ida.shape[0])
+        raised = []
+
+        def src(_user, index, dst, cap, plen, ptype):
+            try:
+                t, data = source(int(index))
+                a = _u8(data)
+                plen[0] = a.size
+                ptype[0] = int(t)
+                if 0 < a.size <= cap:
+                    ctypes.memmove(dst, a.ctypes.data, a.size)
+                return 0
+            except BaseException as e:  # never unwind through C: a non-zero return, re-raised below
+                raised.append(e)
+                return 1
+
+        def sink(_user, off, data, ln):
+            try:
+                on_data(int(off), np.frombuffer((ctypes.c_uint8 * ln).from_address(data), np.uint8) if ln
+                        else np.zeros(0, np.uint8))
+                return 0
+            except BaseException as e:
+                raised.append(e)
+                return 1
+
+        cb_src = _lib.BLOCK_SOURCE(src)
+        cb_sink = _lib.RESTORE_SINK(sink) if on_data is not None else None
+        nbytes, bad_i, first = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        bad_s = ctypes.c_uint32(0)
+        t0 = time.perf_counter()
+        rc = self._L.hbx_restore_file_stream(
+            self._ctx, n, _p(ida), ctypes.cast(cb_src, ctypes.c_void_p), None, int(window_bytes),
+            os.fsencode(out_path) if out_path is not None else None,
+            ctypes.cast(cb_sink, ctypes.c_void_p) if cb_sink is not None else None,
+            os.fsencode(local_path) if local_path is not None else None, int(max_block or 0),
+            ctypes.byref(nbytes), ctypes.byref(bad_i), ctypes.byref(bad_s), ctypes.byref(first))
+        self.last_call_s = time.perf_counter() - t0
+        if raised:
+            raise raised[0]
+        if rc in (_lib.ERR_VERIFY, _lib.ERR_IO):
+            msg = self._L.hbx_last_error(self._ctx)
+            raise RestoreError(f"hbx_restore_file_stream: {_lib.ERRORS.get(rc, rc)}: {msg.decode() if msg else ''}",
+                               rc, int(bad_i.value) if rc == _lib.ERR_VERIFY else None, int(bad_s.value),
+                               int(nbytes.value))
+        self._check(rc, "hbx_restore_file_stream")
+        return int(nbytes.value), int(first.value)
+
+    def restore_file(self, ids, source: Callable[[int], tuple], out_path=None,
+                     on_data: Optional[Callable[[int, np.ndarray], None]] = None, window_bytes: int = 0,
+                     max_block: Optional[int] = None) -> int:
+        """restoreFileData over a whole chain of any length
+        (hashback/restore.go:45-66, 116-135; hbx_restore_file_stream):
+        ``source(i)`` returns block i's ``(type, data field)``; the file is
+        written to ``out_path``, or handed to ``on_data(file_offset, bytes)``
+        window by window, in order (the array is valid during the call only).
+        Host and device memory depend on ``window_bytes`` only.  Returns the
+        bytes restored.  A bad block raises :class:`RestoreError` (its
+        ``bad_index``, ``bad_status``); everything before it was written.
+        An exception raised by ``source`` or ``on_data`` stops the call and is
+        re-raised here.  Neither may call this engine."""
+        if (out_path is None) == (on_data is None):
+            raise ValueError("exactly one of out_path and on_data")
+        return self._restore_stream(ids, source, out_path, on_data, None, window_bytes, max_block)[0]
+
+    def diff_file(self, ids, source: Callable[[int], tuple], local_path, window_bytes: int = 0,
+                  max_block: Optional[int] = None):
+        """diffFileData over a whole chain (hashback/restore.go:249-277):
+        every block verified, its data compared with ``local_path`` at the
+        running offset on the device.  Returns ``(same, first_diff)``:
+        ``first_diff`` is the first differing file offset (the shorter length
+        when one side only ends early), None when the two are equal."""
+        _, first = self._restore_stream(ids, source, None, None, local_path, window_bytes, max_block)
+        return (True, None) if first == _lib.NO_DIFF else (False, first)
 
     def memcpy_h2d_async(self, d_dst: int, h_src: int, nbytes: int):
         """Enqueue an H2D copy on this engine's stream (pinned source)."""

@@ -7,7 +7,8 @@ Reference (fredli74/hashbox):
   ``Serialize``/``Unserialize`` — hashback/hashback.go:80-214;
 * ``storeDir`` (directory block + links + id) — hashback/store.go:201-234;
 * ``storePath`` (what becomes which entry type) — hashback/store.go:254-397;
-* ``entryFromFileInfo`` — hashback/store.go:243-251.
+* ``entryFromFileInfo`` — hashback/store.go:243-251;
+* ``restoreEntry`` / ``restoreDir`` (the way back) — hashback/restore.go:68-162.
 
 Serialization runs in the library's C++ (``hbx_file_entry_*``,
 ``hbx_chain_block_*``, ``hbx_directory_block_*``); directory block ids are
@@ -27,7 +28,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .engine import Engine, FileChunks, HbxError
+from .engine import Engine, FileChunks, HbxError, RestoreError
 
 TYPE_EMPTY, TYPE_DIRECTORY, TYPE_FILE_DATA, TYPE_FILE_CHAIN, TYPE_SYMLINK = 0, 1, 2, 3, 4  # hashback.go:93-99
 
@@ -318,3 +319,76 @@ def store_tree(eng: Engine, root, reference_id: bytes = _ZERO16, io_threads: int
             dir_entry[p].content_block_id = i
     out.seconds = {"walk": t1 - t0, "files": t2 - t1, "directories": time.perf_counter() - t2}
     return out
+
+
+def _read_verified(eng: Engine, read_block, block_id: bytes, what: str) -> bytes:
+    """ReadBlock + VerifyBlock of one directory or chain block: its data,
+    inflated and hashed with its links on the device (Engine.restore_blocks)."""
+    btype, data, links = read_block(bytes(block_id))
+    r = eng.restore_blocks([data], [btype], [block_id], links=[list(links or [])])
+    if r.n_good != 1:
+        raise HbxError(f"{what} block {bytes(block_id).hex()} corrupted (status {int(r.status[0])})")
+    return r.data
+
+
+def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_bytes: int = 0) -> Dict[str, int]:
+    """restoreEntry(root_entry, dest) (hashback/restore.go:68-162): the
+    counterpart of :func:`store_tree`.  ``read_block(id)`` returns a block as
+    it comes off the wire: ``(data type, data field, links)``.
+
+    Directory blocks and chain blocks are inflated and verified on the device
+    with their links (``Engine.restore_blocks``), then parsed
+    (``parse_directory_block`` / ``parse_chain_block``); regular files stream
+    through ``Engine.restore_file`` (every data block verified, the file
+    assembled on the device).  Symbolic links, empty files and directories are
+    created as the reference does; a file is opened with the entry's mode and
+    gets its ModTime (restore.go:108, 141), a directory is chmod-ed after its
+    content (restore.go:99).  Decrypt keys are ignored, as in the reference
+    (restore.go:57).  Returns the counts ``{"files", "directories", "bytes"}``.
+    """
+    dest = os.fsencode(os.fspath(dest))
+    stats = {"files": 0, "directories": 0, "bytes": 0}
+
+    def restore_entry(e: FileEntry, path: bytes):
+        local = os.path.join(path, bytes(e.file_name))
+        if e.file_mode & MODE_SYMLINK:  # restore.go:76-84
+            if e.content_type != TYPE_SYMLINK:
+                raise HbxError(f"invalid ContentType for a symlink ({e.content_type})")
+            os.symlink(bytes(e.file_link), local)
+        elif e.file_mode & MODE_DIR:  # restore.go:85-102
+            os.makedirs(local, 0o777, exist_ok=True)
+            if e.content_type == TYPE_DIRECTORY:
+                for kid in parse_directory_block(_read_verified(eng, read_block, e.content_block_id, "directory")):
+                    restore_entry(kid, local)
+            elif e.content_type != TYPE_EMPTY:
+                raise HbxError(f"invalid ContentType for a directory ({e.content_type})")
+            os.chmod(local, e.file_mode & 0o777)
+            stats["directories"] += 1
+        else:  # restore.go:103-145
+            if e.content_type not in (TYPE_FILE_CHAIN, TYPE_FILE_DATA, TYPE_EMPTY):
+                raise HbxError(f"invalid ContentType for a file ({e.content_type})")
+            # created with the entry's mode, as OpenFile does (restore.go:108: the umask applies)
+            fd = os.open(local, os.O_CREAT | os.O_TRUNC | os.O_WRONLY, e.file_mode & 0o777)
+            mode = stat.S_IMODE(os.fstat(fd).st_mode)
+            os.close(fd)
+            if e.content_type == TYPE_FILE_CHAIN:
+                ids, _keys = parse_chain_block(_read_verified(eng, read_block, e.content_block_id, "chain"))
+            else:
+                ids = [e.content_block_id] if e.content_type == TYPE_FILE_DATA else []
+            if ids:
+                # The reference writes through the handle it created; the engine opens the path again, which a
+                # mode without the owner's write bit (0444) would refuse: writable while written, then the mode
+                # the creation gave it.
+                if not mode & stat.S_IWUSR:
+                    os.chmod(local, mode | stat.S_IWUSR)
+                try:
+                    stats["bytes"] += eng.restore_file(ids, lambda i: read_block(bytes(ids[i]))[:2], out_path=local,
+                                                       window_bytes=window_bytes)
+                finally:
+                    if not mode & stat.S_IWUSR:
+                        os.chmod(local, mode)
+            os.utime(local, ns=(time.time_ns(), int(e.mod_time)))
+            stats["files"] += 1
+
+    restore_entry(root_entry, dest)
+    return stats

@@ -26,6 +26,10 @@
  *   hbx_directory_block_* and storeDir's block id (store.go:201-234)
  *   hbx_deflate_blocks    HashboxBlock.CompressData, zlib (block.go:133-184)
  *   hbx_inflate_blocks_device  UncompressData (block.go:113-131), on the device
+ *   hbx_restore_blocks    restoreFileData / diffFileData over a block chain
+ *                         (hashback/restore.go:45-66, 249-277): UncompressData,
+ *                         VerifyBlock and the file's bytes in one call
+ *   hbx_restore_file_stream  the same for a chain of any length, in windows
  *   hbx_wire_*            ProtocolMessage framing of every message type
  *                         (pkg/core/protocol.go:184-264), block-store encoders
  *
@@ -491,7 +495,11 @@ int hbx_verify_submit_device(hbx_ctx *ctx, const void *d_arena, uint64_t n, cons
  * 4 invalid code, 5 distance too far back, 6 bad stored length.  Any RFC
  * 1950 stream (Go's compress/zlib, K7's).  A corrupt stream only sets its
  * status.  Then hbx_verify_blocks_device / hbx_verify_submit_device on the
- * output is VerifyBlock of compressed blocks (block.go:152-166).
+ * output is VerifyBlock of compressed blocks (block.go:152-166).  This call
+ * needs each stream's inflated size in advance; a block read back from a
+ * server carries its compressed length only (Unserialize, block.go:82-94):
+ * hbx_restore_blocks / hbx_restore_file_stream below inflate, verify and
+ * assemble such blocks without it.
  * Synchronous; refused (HBX_ERR_STATE) while batches are pending. */
 int hbx_inflate_blocks_device(hbx_ctx *ctx, const void *d_in, uint64_t n, const uint64_t *in_offs,
                               const uint64_t *in_lens, void *d_out, const uint64_t *out_offs,
@@ -683,6 +691,100 @@ int hbx_store_file_stream(hbx_ctx *ctx, const char *path, uint64_t file_len, uin
                           uint32_t io_threads, uint32_t flags, hbx_idset *set,
                           hbx_seg_sink_fn sink, void *user, hbx_file_summary *summary);
 
+/* ---- Restore and diff: a file's block chain back into its bytes (K10) ---------
+ * restoreFileData (hashback/restore.go:45-66) reads each block of a file's
+ * chain, VerifyBlock()s it (restore.go:52-54; UncompressData + HashData,
+ * block.go:113-131, 152-174) and appends its data to the file; diffFileData
+ * (restore.go:249-277) compares each verified block with the local file at the
+ * running offset instead.  These calls take the blocks as they come off the
+ * wire (Unserialize, block.go:82-94: the data field, its DataType, and the
+ * BlockID that was asked for; the inflated size is NOT known) and give the
+ * file's bytes, or the first difference from a local copy.  The same path
+ * serves the server's write check (server/server.go:182) and verify -content
+ * (pkg/storagedb/integrity.go:117, 282) with directory and chain blocks: links
+ * are passed through to the hash. */
+#define HBX_BLOCK_RAW 0xff          /* BlockDataTypeRaw,  block.go:22-23 */
+#define HBX_BLOCK_ZLIB 0x01         /* BlockDataTypeZlib */
+#define HBX_MAX_BLOCK (8u << 20)    /* MAX_BLOCK_SIZE, hashback.go:37 */
+#define HBX_ERR_VERIFY (-9)         /* hbx_restore_file_stream: a block of the chain is bad */
+/* The largest data field accepted for a block whose data is at most max_block
+ * bytes (0 = HBX_MAX_BLOCK): at least hbx_deflate_bound(max_block), so every
+ * stream K7 or Go's compress/zlib writes for such a block fits.  Pure host
+ * arithmetic. */
+uint64_t hbx_restore_in_bound(uint64_t max_block);
+/* n blocks of one chain, in file order, in host memory: block i's data field
+ * is datas[i][0 .. lens[i]), of type types[i] (HBX_BLOCK_RAW: the data itself;
+ * HBX_BLOCK_ZLIB: one zlib stream), and must hash to expect[16 i ..] with its
+ * links (links / link_base / n_links as hbx_verify_blocks, all NULL when no
+ * block has links).  max_block (0 = HBX_MAX_BLOCK) is the largest block data
+ * accepted.  status[i] receives
+ *   0      the block inflated and its ID matches (VerifyBlock true);
+ *   1..6   exactly hbx_inflate_blocks_device's values; a stream (or a raw
+ *          block) longer than max_block is 3;
+ *   7      the ID does not match (VerifyBlock false);
+ *   8      the data field is longer than hbx_restore_in_bound(max_block), or
+ *          the type is neither raw nor zlib.
+ * The reference stops at the first bad block (restore.go:52-54), so the
+ * result is a PREFIX: *n_good = the number of leading blocks with status 0,
+ * offs[0 .. *n_good] (offs holds n + 1) the file offset where each of them
+ * starts (offs[i + 1] - offs[i] = block i's length) and, with out != NULL,
+ * out[0 .. offs[*n_good]) the file's bytes.  Nothing past out[offs[*n_good]) is
+ * written.  A corrupt block is a result, not an error: the call returns HBX_OK.
+ * Diff mode (out NULL, local != NULL: the local copy's local_len bytes, host
+ * memory): nothing is written; *first_diff = the smallest offset inside the
+ * good prefix at which the two differ, comparing the bytes present on both
+ * sides; else min(local_len, offs[*n_good]) if the lengths differ; else
+ * UINT64_MAX.  (The caller compares file sizes first, restore.go:322, and
+ * prints the 16-byte line.)
+ * HBX_ERR_ARG: out and local both set or both NULL, out_cap smaller than the
+ * good prefix, max_block above 1 GiB.  HBX_ERR_STATE while batches are
+ * pending.  Device memory: a slot of max_block per zlib block, so long chains
+ * run in windows of as many blocks as a quarter of the free device memory
+ * holds.  Synchronous. */
+int hbx_restore_blocks(hbx_ctx *ctx, uint64_t n, const uint8_t *const *datas, const uint64_t *lens,
+                       const uint8_t *types, const uint8_t *expect, const uint8_t *links,
+                       const uint64_t *link_base, const uint32_t *n_links, uint64_t max_block, uint8_t *out,
+                       uint64_t out_cap, const uint8_t *local, uint64_t local_len, uint64_t *offs,
+                       uint32_t *status, uint64_t *n_good, uint64_t *first_diff);
+/* Block `index` of the chain into dst[0 .. cap) (pinned staging memory of the
+ * engine): *len = its data field's length, *type = its DataType.  Non-zero =
+ * failure.  A field longer than cap cannot be delivered: report its length
+ * (the block then gets status 8) and write nothing. */
+typedef int (*hbx_block_source_fn)(void *user, uint64_t index, uint8_t *dst, uint64_t cap, uint64_t *len,
+                                   uint8_t *type);
+/* The file's bytes [file_off, file_off + len), valid during the call. */
+typedef int (*hbx_restore_sink_fn)(void *user, uint64_t file_off, const uint8_t *data, uint64_t len);
+/* restoreFileData / diffFileData for a chain of any length (restore.go:45-66,
+ * 249-277): block i has the ID ids[16 i ..] (the FileChainBlock's list, or
+ * the one ContentBlockID of a single-block file) and is fetched with
+ * source(user, i, ...).  Exactly one of out_path (the file is created or
+ * truncated and written), sink (the bytes are handed over in file order) and
+ * local_path (diff mode, as above, against that file; *first_diff required)
+ * is set.  The chain runs in WINDOWS of as many blocks as fit window_bytes of
+ * inflate slots (max_block + 256 each; 0 = 1 GiB; at least one block), two in
+ * flight: the source fills window k + 1's pinned staging and its copy to the
+ * device runs while window k inflates; window k's blocks are verified beside
+ * their gather into a pinned buffer, whose good prefix is written (or sunk) by
+ * a worker thread while window k + 1 inflates.  source runs on an engine
+ * thread, one call at a time in index order; sink likewise, once per window
+ * with contiguous ascending offsets; neither may call into the same context.
+ * Memory depends on window_bytes and max_block only: with W blocks per window,
+ * device W slots + 2 W hbx_restore_in_bound (+ W max_block in diff mode), pinned
+ * host 2 W hbx_restore_in_bound + 2 W max_block (about 4.2 GiB pinned at the
+ * defaults, W = 127).  The buffers are kept for the next call and freed by
+ * hbx_ctx_destroy.
+ * The first bad block ends the call with HBX_ERR_VERIFY, *bad_index its index
+ * and *bad_status its status (as hbx_restore_blocks); the blocks before it
+ * were written or sunk, nothing at or past it.  A failing source, sink or
+ * write, or a local file that cannot be read, is HBX_ERR_IO.  Diff mode stops
+ * at the first window that holds a difference.  *bytes = the bytes restored
+ * (compared).  In every case the engine's streams are drained and the context
+ * stays usable.  Synchronous; HBX_ERR_STATE while batches are pending. */
+int hbx_restore_file_stream(hbx_ctx *ctx, uint64_t n_blocks, const uint8_t *ids, hbx_block_source_fn src,
+                            void *user, uint64_t window_bytes, const char *out_path, hbx_restore_sink_fn sink,
+                            const char *local_path, uint64_t max_block, uint64_t *bytes, uint64_t *bad_index,
+                            uint32_t *bad_status, uint64_t *first_diff);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
@@ -708,7 +810,10 @@ int hbx_free_pinned(void *p);
 /* The context's effective pipeline knobs as one JSON object (NUL-terminated,
  * at most cap bytes): slice, join lag, K1 tile and run, K3 waves and placement,
  * and whether the HBX_* A/B environment switches were honoured (ab_env: they
- * are read only when HBX_AB=1).  No reference counterpart: diagnostics. */
+ * are read only when HBX_AB=1); restore_ms: the host milliseconds the latest
+ * hbx_restore_* call spent staging its input, inflating, verifying beside
+ * K10, and copying out, each phase ending on a synchronization.  No reference
+ * counterpart: diagnostics. */
 int hbx_knobs(hbx_ctx *ctx, char *out, uint64_t cap);
 
 /* Device time (ms) of the last completed batch per stage:
