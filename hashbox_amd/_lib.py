@@ -41,6 +41,7 @@ EXPORTS = [
     "hbx_idset_stats", "hbx_idset_export", "hbx_idset_truncate", "hbx_submit_device_dd", "hbx_store_paths_dd",
     "hbx_seg_submit_device_dd", "hbx_store_file_stream",
     "hbx_restore_in_bound", "hbx_restore_blocks", "hbx_restore_file_stream",
+    "hbx_restore_many_window", "hbx_restore_files_blocks", "hbx_restore_files_stream",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -110,9 +111,21 @@ SEG_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(SegChu
 BLOCK_SOURCE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                 ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8))
 RESTORE_SINK = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64)
+# hbx_file_block_source_fn (include/hbxgpu.h)
+FILE_BLOCK_SOURCE = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                     ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8))
+
+
+class RestoredFile(ctypes.Structure):
+    """hbx_restored_file: one file's result of hbx_restore_files_stream."""
+    _fields_ = [("bytes", ctypes.c_uint64), ("n_good", ctypes.c_uint64), ("bad_index", ctypes.c_uint64),
+                ("first_diff", ctypes.c_uint64), ("bad_status", ctypes.c_uint32), ("err", ctypes.c_int32)]
+
+
 BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
 MAX_BLOCK = 8 << 20                 # HBX_MAX_BLOCK
 ERR_IO, ERR_VERIFY = -4, -9
+ERR_CAPACITY = -3
 NO_DIFF = (1 << 64) - 1             # first_diff when nothing differs
 
 _lib = None
@@ -240,6 +253,9 @@ def load() -> ctypes.CDLL:
     L.hbx_restore_blocks.argtypes = [P, U64, P, P, P, P, P, P, P, U64, P, U64, P, U64, P, P, PU64, PU64]
     L.hbx_restore_file_stream.argtypes = [P, U64, P, P, P, U64, ctypes.c_char_p, P, ctypes.c_char_p, U64, PU64, PU64,
                                           PU32, PU64]
+    L.hbx_restore_many_window.argtypes = [U64, P, U64, U64, PU64]
+    L.hbx_restore_files_blocks.argtypes = [P, U64, P, P, P, P, P, P, P, P, P, U64, P, U64, P, P, P, P, P, P, P]
+    L.hbx_restore_files_stream.argtypes = [P, U64, P, P, P, P, P, U64, P, P, ctypes.c_uint32, U64, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

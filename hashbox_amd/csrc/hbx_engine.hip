@@ -42,6 +42,7 @@
 #include "hbx_inflate_split.hip"
 #include "hbx_dedup.hip"
 #include "hbx_restore.hip"
+#include "hbx_restore_many.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 
@@ -379,6 +380,9 @@ struct hbx_ctx {
   // image / the local copy (diff), the piece table, the diff word; the pinned
   // staging and output of two windows; the stream the next window is filled on
   DevBuf d_rin[2], d_rslots, d_rimg, d_rpiece, d_rword;
+  DevBuf d_rretry;  // hbx_restore_files_*: max_block slots of the streams that outgrew their size hint
+  // the latest hbx_restore_files_* call: staged windows, K11 passes, streams inflated again
+  uint64_t many_windows = 0, many_passes = 0, many_retries = 0;
   PinBuf h_rin[2], h_rout[2];
   hipStream_t fstream = nullptr;
   // host ms of the latest hbx_restore_* call per phase, each ending on a
@@ -1835,7 +1839,7 @@ void hbx_ctx_destroy(hbx_ctx* c) {
                     &c->d_vout, &c->d_vexp, &c->d_zeros, &c->d_zblk, &c->d_zinfo, &c->d_zoff,
                     &c->d_zlen, &c->d_zout, &c->d_zimg, &c->d_idesc, &c->d_ires, &c->d_sreg, &c->d_sstart,
                     &c->d_sres, &c->d_sscratch, &c->d_smeta, &c->d_rin[0], &c->d_rin[1], &c->d_rslots, &c->d_rimg,
-                    &c->d_rpiece, &c->d_rword})
+                    &c->d_rpiece, &c->d_rword, &c->d_rretry})
     b->release();
   for (PinBuf* h : {&c->h_rin[0], &c->h_rin[1], &c->h_rout[0], &c->h_rout[1]}) h->release();
   if (c->fstream) {
@@ -2030,13 +2034,14 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"plan_cut\": %u, \"k1_swz\": %u, \"k3_psets\": %u, \"d2h_kernel\": %u, \"k8_split_streams\": %llu, "
       "\"k8_split_fallbacks\": %llu, \"gate_meta\": %u, \"sdma_warm\": %u, \"sdma_h2d_mask\": %u, "
       "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
-      "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f]}",
+      "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu]}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
       (unsigned long long)c->k8_split_streams, (unsigned long long)c->k8_split_fallbacks, c->gate_meta,
       c->sdma_warm, c->sdma_h2d, c->sdma_d2h, c->sdma_warm_ms, c->k3_spin, c->plan_addr, c->plan_addr_shift, c->k1_ext, c->k1_dma4, c->k1_early,
-      c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3]);
+      c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3],
+      (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -4756,6 +4761,764 @@ int hbx_restore_file_stream(hbx_ctx* c, uint64_t n_blocks, const uint8_t* ids, h
   if (bytes) *bytes = file_off;
   if (rc == HBX_OK && local_path && *first_diff == hbxr::kNoDiff && local_len != file_off)
     *first_diff = std::min(local_len, file_off);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- restore and diff of many files (hbx_restore_many.hip, K11) ---------------
+namespace {
+
+constexpr uint64_t kManyWindow = 1ull << 30;  // window_bytes = 0
+
+// One block's share of a window: its capacity, K6's read slack, a multiple of 256.
+inline uint64_t many_slot(uint64_t cap) {
+  return ((std::min<uint64_t>(cap, 1ull << 62) + 255ull) & ~255ull) + 256ull;
+}
+
+// hbx_restore_many_window's rule: the blocks from `start` whose shares fit wb, at least one.
+uint64_t many_window_end(uint64_t n, const uint64_t* caps, uint64_t wb, uint64_t start) {
+  uint64_t sum = 0, e = start;
+  while (e < n) {
+    const uint64_t s = many_slot(caps[e]);
+    if (e > start && (s > wb || sum > wb - s)) break;
+    sum += s;
+    e++;
+  }
+  return e;
+}
+
+// The staged input of a window may hold this many bytes: data fields are about
+// as long as their capacities (a stored deflate block adds 5 bytes per 32 KiB),
+// and one that is not (a tiny size hint in front of a long stream) ends the
+// window early instead of growing the buffer.
+inline uint64_t many_stage_cap(uint64_t wb, uint64_t in_slot) { return wb + wb / 512 + 2 * in_slot + 4096; }
+
+// One window's blocks, their data fields in device memory.
+struct ManyStaged {
+  uint64_t first = 0, n = 0;  // global index of block 0; blocks
+  bool last = false;          // (stream) nothing follows this window
+  std::vector<uint64_t> src, lens, caps;  // device address and length of the data field; capacity (raw: its length)
+  std::vector<uint8_t> types, hinted;     // DataType; the capacity comes from a size hint
+  std::vector<uint32_t> status, file;     // 0 or 8 from the pre-check, then the block's status; its file
+  std::string err;
+  void clear(uint64_t at) {
+    first = at;
+    n = 0;
+    last = false;
+    for (auto* v : {&src, &lens, &caps}) v->clear();
+    types.clear();
+    hinted.clear();
+    status.clear();
+    file.clear();
+    err.clear();
+  }
+  void push(uint64_t s, uint64_t len, uint64_t cap, uint8_t type, bool hint, uint32_t st, uint32_t f) {
+    src.push_back(s);
+    lens.push_back(len);
+    caps.push_back(cap);
+    types.push_back(type);
+    hinted.push_back(hint ? 1 : 0);
+    status.push_back(st);
+    file.push_back(f);
+    n++;
+  }
+};
+
+// The blocks [b0, b1) of one file inside one K11 pass.
+struct ManySeg {
+  uint32_t file = 0;
+  uint64_t b0 = 0, b1 = 0;  // in the staged window
+  uint64_t img = 0;         // where its bytes start in the pass's packed image
+  uint64_t foff0 = 0;       // the file offset they start at (the file's good bytes so far)
+  uint64_t bytes = 0;       // what K11 touches: the blocks before the first that failed to inflate
+  uint64_t good = 0;        // the bytes of its leading verified blocks
+  bool was_bad = false;     // the file had a bad block in an earlier pass
+  uint64_t have = 0, loff = 0;  // diff: bytes of the local copy in [foff0, foff0 + bytes), their place in the local image
+};
+
+using ManyLocalFn = std::function<int(std::vector<ManySeg>&, const uint8_t**, uint64_t*)>;
+using ManyEmitFn = std::function<int(const std::vector<ManySeg>&, const uint8_t*)>;
+
+// What one hbx_restore_files_* call carries from window to window.
+struct ManyRun {
+  uint64_t mb = HBX_MAX_BLOCK, wb = kManyWindow;
+  const uint8_t* expect = nullptr;
+  const uint8_t* links = nullptr;
+  const uint64_t* link_base = nullptr;
+  const uint32_t* n_links = nullptr;
+  bool diff = false;
+  std::vector<uint64_t> run, ngood, found;  // per file: good bytes and blocks so far, smallest differing offset
+  std::vector<uint8_t> bad;                 // per file: a bad block was met
+  std::vector<uint32_t> bad_status;
+  uint64_t* blk_offs = nullptr;   // per global block (may be NULL)
+  uint32_t* status_out = nullptr; // per global block (may be NULL)
+  uint64_t pass = 0;
+  ManyLocalFn local;  // diff: the local bytes of the pass's segments (have, loff) in pinned memory
+  ManyEmitFn emit;    // gather: the pass's packed image (pinned memory), after its checks
+  void init(uint64_t n_files) {
+    run.assign(n_files, 0);
+    ngood.assign(n_files, 0);
+    found.assign(n_files, hbxr::kNoDiff);
+    bad.assign(n_files, 0);
+    bad_status.assign(n_files, 0);
+  }
+};
+
+// One pass over the blocks [s, e) of a staged window, already inflated (addr,
+// dlen, status): K11 (result stream) beside VerifyBlock (K6, scan stream), as
+// restore_window does for one chain, with the image in pinned host memory and
+// its guard bytes checked.  Every stream is idle on return, also on failure.
+int many_pass(hbx_ctx* c, ManyRun& R, ManyStaged& S, uint64_t s, uint64_t e, const std::vector<uint64_t>& addr,
+              const std::vector<uint64_t>& dlen) {
+  const uint64_t n = e - s;
+  if (n == 0) return HBX_OK;
+  c->many_passes++;
+  const auto t_verify = std::chrono::steady_clock::now();
+  // the packed layout before VerifyBlock's answer: per file, the blocks before the first that did not inflate
+  std::vector<ManySeg> segs;
+  std::vector<uint64_t> bimg(n, 0), bfoff(n, 0);
+  std::vector<uint8_t> live(n, 0);
+  uint64_t total = 0;
+  bool open = false;
+  for (uint64_t i = s; i < e; i++) {
+    const uint32_t f = S.file[i];
+    if (segs.empty() || segs.back().file != f) {
+      ManySeg g;
+      g.file = f;
+      g.b0 = i;
+      g.img = total;
+      g.foff0 = R.run[f];
+      g.was_bad = R.bad[f] != 0;
+      segs.push_back(g);
+      open = !g.was_bad;
+    }
+    ManySeg& g = segs.back();
+    g.b1 = i + 1;
+    if (open && S.status[i] == 0) {
+      live[i - s] = 1;
+      bimg[i - s] = total;
+      bfoff[i - s] = g.foff0 + g.bytes;
+      g.bytes += dlen[i];
+      total += dlen[i];
+    } else {
+      open = false;
+    }
+  }
+  if (segs.size() > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "restore: window too large");
+  hipStream_t rs = c->rstream;
+  const uint8_t* h_local = nullptr;
+  uint64_t local_total = 0;
+  uint8_t* image = nullptr;
+  if (R.diff) {
+    if (int rc = R.local(segs, &h_local, &local_total)) return rc;
+  } else {
+    PinBuf& hb = c->h_rout[R.pass & 1];
+    HBX_TRY(c, hb.ensure(kImageLead + total + kImageGuard));
+    image = hb.as<uint8_t>() + kImageLead;
+  }
+  R.pass++;
+  std::vector<hbxm::Piece> pieces;
+  for (uint64_t k = 0; k < segs.size(); k++) {
+    const ManySeg& g = segs[k];
+    const uint64_t cover = R.diff ? std::min(g.have, g.bytes) : g.bytes;  // bytes of the segment K11 touches
+    for (uint64_t i = g.b0; i < g.b1; i++) {
+      if (!live[i - s]) continue;
+      const uint64_t at = bfoff[i - s] - g.foff0;  // inside the segment
+      if (at >= cover) break;
+      const uint64_t len = std::min(dlen[i], cover - at);
+      const uint64_t dst = R.diff ? g.loff + at : bimg[i - s];
+      for (uint64_t p = 0; p < len; p += hbxm::kPieceMany)
+        pieces.push_back(hbxm::Piece{addr[i] + p, dst + p, bfoff[i - s] + p,
+                                     (uint32_t)std::min<uint64_t>(hbxm::kPieceMany, len - p), (uint32_t)k});
+    }
+  }
+  if (pieces.size() > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "restore: window too large");
+  std::vector<uint64_t> words(R.diff ? segs.size() : 0, hbxr::kNoDiff);
+  const bool guarded = !R.diff && !pieces.empty();
+  const uint32_t groups = (uint32_t)((pieces.size() + hbxm::kWaves - 1) / hbxm::kWaves);
+  int krc = HBX_OK;
+  if (!pieces.empty()) {
+    krc = [&]() -> int {
+      HBX_TRY(c, c->d_rpiece.ensure(pieces.size() * sizeof(hbxm::Piece)));
+      HBX_TRY(c, hipMemcpyAsync(c->d_rpiece.p, pieces.data(), pieces.size() * sizeof(hbxm::Piece),
+                                hipMemcpyHostToDevice, rs));
+      if (R.diff) {
+        HBX_TRY(c, c->d_rimg.ensure(local_total + 256));
+        HBX_TRY(c, hipMemsetAsync(c->d_rword.p, 0xFF, 8 * segs.size(), rs));
+        if (local_total)
+          HBX_TRY(c, hipMemcpyAsync(c->d_rimg.p, h_local, local_total, hipMemcpyHostToDevice, rs));
+        hipLaunchKernelGGL(hbx_k11_diff, dim3(groups), dim3(hbxm::kThreads), 0, rs, c->d_rpiece.as<hbxm::Piece>(),
+                           (uint32_t)pieces.size(), c->d_rimg.as<uint8_t>(), c->d_rword.as<unsigned long long>());
+        HBX_TRY(c, hipGetLastError());
+        HBX_TRY(c, hipMemcpyAsync(words.data(), c->d_rword.p, 8 * segs.size(), hipMemcpyDeviceToHost, rs));
+      } else {
+        std::memset(image - kImageGuard, kGuardByte, kImageGuard);
+        std::memset(image + total, kGuardByte, kImageGuard);
+        hipLaunchKernelGGL(hbx_k11_gather, dim3(groups), dim3(hbxm::kThreads), 0, rs, c->d_rpiece.as<hbxm::Piece>(),
+                           (uint32_t)pieces.size(), image);
+        HBX_TRY(c, hipGetLastError());
+      }
+      return HBX_OK;
+    }();
+  }
+  // VerifyBlock of every block that inflated, links passed through
+  std::vector<uint32_t> nl(n, 0u);
+  if (R.n_links)
+    for (uint64_t i = s; i < e; i++)
+      if (S.status[i] == 0) nl[i - s] = R.n_links[S.first + i];
+  std::vector<uint8_t> ok(n, 0);
+  int vrc = krc ? HBX_OK
+                : verify_device(c, nullptr, n, addr.data() + s, dlen.data() + s, R.links,
+                                R.link_base ? R.link_base + S.first + s : nullptr, nl.data(), nullptr,
+                                R.expect + 16 * (S.first + s), ok.data(), nullptr);
+  const std::string verr = c->err;
+  const int src_ = c->hip(hipStreamSynchronize(rs), "hipStreamSynchronize(result stream)");
+  c->restore_ms[2] += ms_since(t_verify);
+  if (krc) return krc;
+  if (vrc) return c->fail(vrc, verr);
+  if (src_) return src_;
+  if (guarded)
+    for (uint64_t b = 0; b < kImageGuard; b++)
+      if ((image - kImageGuard)[b] != kGuardByte || image[total + b] != kGuardByte)
+        return c->fail(HBX_ERR_STATE, "restore: K11 wrote outside the image");
+  for (uint64_t i = s; i < e; i++)
+    if (S.status[i] == 0 && !ok[i - s]) S.status[i] = 7;
+  // per file: its leading good blocks of this pass join its prefix
+  for (uint64_t k = 0; k < segs.size(); k++) {
+    ManySeg& g = segs[k];
+    const uint32_t f = g.file;
+    uint64_t i = g.b0;
+    if (!g.was_bad) {
+      while (i < g.b1 && S.status[i] == 0) {
+        if (R.blk_offs) R.blk_offs[S.first + i] = g.foff0 + g.good;
+        g.good += dlen[i];
+        i++;
+      }
+      R.ngood[f] += i - g.b0;
+      R.run[f] += g.good;
+      if (i < g.b1) {
+        R.bad[f] = 1;
+        R.bad_status[f] = S.status[i];
+      }
+      if (R.diff && words[k] < g.foff0 + g.good) R.found[f] = std::min(R.found[f], words[k]);
+    }
+    for (; i < g.b1; i++)
+      if (R.blk_offs) R.blk_offs[S.first + i] = ~0ull;
+  }
+  if (R.status_out)
+    for (uint64_t i = s; i < e; i++) R.status_out[S.first + i] = S.status[i];
+  if (!R.diff && R.emit) {
+    const auto t_out = std::chrono::steady_clock::now();
+    const int rc = R.emit(segs, image);
+    c->restore_ms[3] += ms_since(t_out);
+    return rc;
+  }
+  return HBX_OK;
+}
+
+// A staged window: inflate every zlib block into a slot of its (hinted)
+// capacity, then K11 passes over it.  A size hint is never trusted: a stream
+// that overflows a slot smaller than max_block is inflated again into a
+// max_block slot, and the window is then cut into passes by the window rule
+// over the corrected capacities, so no pass holds more than the window allows.
+int many_process(hbx_ctx* c, ManyRun& R, ManyStaged& S) {
+  const uint64_t n = S.n;
+  if (n == 0) return HBX_OK;
+  c->many_windows++;
+  // (the diff words of a pass, one per file in it; also the address of a block that has no data: never
+  // reallocated while a pass is under way)
+  HBX_TRY(c, c->d_rword.ensure(std::max<uint64_t>(4096, 8 * n)));
+  const uint64_t mb = R.mb;
+  auto estimate = [&](uint64_t len) { return std::min<uint64_t>(mb, 8 * len + 4096); };  // as restore_window
+  std::vector<uint64_t> zi, in_offs, in_lens, out_offs, out_caps, out_hint, out_lens;
+  std::vector<uint32_t> zst;
+  uint64_t slots = 0;
+  for (uint64_t i = 0; i < n; i++)
+    if (S.status[i] == 0 && S.types[i] == HBX_BLOCK_ZLIB) {
+      zi.push_back(i);
+      in_offs.push_back(S.src[i]);
+      in_lens.push_back(S.lens[i]);
+      out_offs.push_back(slots);
+      out_caps.push_back(S.caps[i]);
+      out_hint.push_back(S.hinted[i] ? S.caps[i] : estimate(S.lens[i]));
+      slots += many_slot(S.caps[i]);
+    }
+  const uint64_t nz = zi.size();
+  const auto t_inflate = std::chrono::steady_clock::now();
+  out_lens.assign(nz, 0);
+  zst.assign(nz, 0);
+  if (nz) {
+    HBX_TRY(c, c->d_rslots.ensure(slots + 65536));
+    if (int rc = inflate_device(c, nullptr, nz, in_offs.data(), in_lens.data(), c->d_rslots.p, out_offs.data(),
+                                out_caps.data(), out_lens.data(), zst.data(), out_hint.data()))
+      return rc;
+  }
+  c->restore_ms[1] += ms_since(t_inflate);
+  std::vector<uint64_t> addr(n), dlen(n, 0), newcaps(S.caps);
+  std::vector<uint8_t> over(n, 0);
+  const uint64_t nowhere = reinterpret_cast<uint64_t>(c->d_rword.p);
+  for (uint64_t i = 0; i < n; i++) {
+    addr[i] = nowhere;
+    if (S.status[i] == 0 && S.types[i] == HBX_BLOCK_RAW) {
+      if (S.lens[i] > mb) {
+        S.status[i] = hbxi::kErrOutput;
+      } else {
+        addr[i] = S.src[i];
+        dlen[i] = S.lens[i];
+      }
+    }
+  }
+  for (uint64_t k = 0; k < nz; k++) {
+    const uint64_t i = zi[k];
+    S.status[i] = zst[k];
+    if (zst[k] == 0) {
+      addr[i] = reinterpret_cast<uint64_t>(c->d_rslots.p) + out_offs[k];
+      dlen[i] = out_lens[k];
+    } else if (zst[k] == hbxi::kErrOutput && S.caps[i] < mb) {
+      over[i] = 1;
+      newcaps[i] = mb;
+    }
+  }
+  const uint64_t stride = restore_stride(mb);
+  for (uint64_t s = 0; s < n;) {
+    const uint64_t e = many_window_end(n, newcaps.data(), R.wb, s);
+    std::vector<uint64_t> ri, r_in, r_len, r_out, r_cap, r_hint, r_olen;
+    for (uint64_t i = s; i < e; i++)
+      if (over[i]) {
+        r_out.push_back(ri.size() * stride);
+        ri.push_back(i);
+        r_in.push_back(S.src[i]);
+        r_len.push_back(S.lens[i]);
+        r_cap.push_back(mb);
+        r_hint.push_back(estimate(S.lens[i]));
+      }
+    if (!ri.empty()) {
+      const auto t_again = std::chrono::steady_clock::now();
+      c->many_retries += ri.size();
+      std::vector<uint32_t> rst(ri.size(), 0);
+      r_olen.assign(ri.size(), 0);
+      HBX_TRY(c, c->d_rretry.ensure(ri.size() * stride + 65536));
+      if (int rc = inflate_device(c, nullptr, ri.size(), r_in.data(), r_len.data(), c->d_rretry.p, r_out.data(),
+                                  r_cap.data(), r_olen.data(), rst.data(), r_hint.data()))
+        return rc;
+      for (uint64_t k = 0; k < ri.size(); k++) {
+        const uint64_t i = ri[k];
+        S.status[i] = rst[k];
+        if (rst[k] == 0) {
+          addr[i] = reinterpret_cast<uint64_t>(c->d_rretry.p) + r_out[k];
+          dlen[i] = r_olen[k];
+        }
+      }
+      c->restore_ms[1] += ms_since(t_again);
+    }
+    if (int rc = many_pass(c, R, S, s, e, addr, dlen)) return rc;
+    s = e;
+  }
+  return HBX_OK;
+}
+
+// Up to `threads` threads over the jobs [0, n); the caller's thread is one of them.
+template <class F>
+void many_pool(uint32_t threads, uint64_t n, F&& job) {
+  if (n == 0) return;
+  std::atomic<uint64_t> next{0};
+  auto work = [&] {
+    for (uint64_t j = next.fetch_add(1); j < n; j = next.fetch_add(1)) job(j);
+  };
+  const uint64_t nt = std::min<uint64_t>(std::max<uint32_t>(threads, 1u), n);
+  std::vector<std::thread> th;
+  for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+  work();
+  for (auto& t : th) t.join();
+}
+
+// The capacity of a block of file f: a zlib block's is min(max_block, hint), a raw block's its length.
+inline uint64_t many_cap(uint64_t mb, const uint64_t* hint, uint64_t f, uint8_t type, uint64_t len, bool* hinted) {
+  *hinted = false;
+  if (type == HBX_BLOCK_RAW) return len;
+  if (hint && hint[f]) {
+    *hinted = true;
+    return std::min(mb, hint[f]);
+  }
+  return mb;
+}
+
+bool many_first_ok(uint64_t n_files, const uint64_t* first) {
+  if (n_files == 0) return true;
+  if (!first || first[0] != 0) return false;
+  for (uint64_t f = 0; f < n_files; f++)
+    if (first[f + 1] < first[f]) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hbx_restore_many_window(uint64_t n, const uint64_t* caps, uint64_t window_bytes, uint64_t start, uint64_t* end) {
+  if (!end || start > n || (n && !caps)) return HBX_ERR_ARG;
+  *end = many_window_end(n, caps, window_bytes ? window_bytes : kManyWindow, start);
+  return HBX_OK;
+}
+
+int hbx_restore_files_blocks(hbx_ctx* c, uint64_t n_files, const uint64_t* first, const uint8_t* const* datas,
+                             const uint64_t* lens, const uint8_t* types, const uint8_t* expect, const uint8_t* links,
+                             const uint64_t* link_base, const uint32_t* n_links, const uint64_t* size_hint,
+                             uint64_t max_block, uint8_t* out, uint64_t out_cap, uint64_t* out_offs,
+                             const uint8_t* local, const uint64_t* local_offs, uint64_t* blk_offs, uint32_t* status,
+                             uint64_t* n_good, uint64_t* first_diff) {
+  if (!c || (n_files && (!first || !n_good))) return HBX_ERR_ARG;
+  if ((out != nullptr) == (local != nullptr)) return HBX_ERR_ARG;  // exactly one target
+  if (out && !out_offs) return HBX_ERR_ARG;
+  if (local && (!local_offs || !first_diff)) return HBX_ERR_ARG;
+  if (!many_first_ok(n_files, first)) return HBX_ERR_ARG;
+  const uint64_t n = n_files ? first[n_files] : 0;
+  if (n && (!datas || !lens || !types || !expect || !status)) return HBX_ERR_ARG;
+  const uint64_t mb = restore_mb(max_block);
+  if (mb > kRestoreMaxBlock || n > 0x7FFFFFFFull || n_files > 0x7FFFFFFFull) return HBX_ERR_ARG;
+  if (local)
+    for (uint64_t f = 0; f < n_files; f++)
+      if (local_offs[f + 1] < local_offs[f]) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  for (double& t : c->restore_ms) t = 0.0;
+  c->many_windows = c->many_passes = c->many_retries = 0;
+  const uint64_t bound = hbx_restore_in_bound(mb), in_slot = (bound + 15) & ~15ull;
+  ManyRun R;
+  R.mb = mb;
+  R.wb = kManyWindow;
+  R.expect = expect;
+  R.links = links;
+  R.link_base = link_base;
+  R.n_links = n_links;
+  R.diff = local != nullptr;
+  R.blk_offs = blk_offs;
+  R.status_out = status;
+  R.init(n_files);
+  if (out_offs) out_offs[0] = 0;
+  // per block: file, pre-check, capacity
+  std::vector<uint32_t> file(n), pre(n);
+  std::vector<uint64_t> caps(n);
+  std::vector<uint8_t> hinted(n);
+  for (uint64_t f = 0; f < n_files; f++)
+    for (uint64_t i = first[f]; i < first[f + 1]; i++) {
+      const bool known = types[i] == HBX_BLOCK_RAW || types[i] == HBX_BLOCK_ZLIB;
+      pre[i] = (!known || lens[i] > bound) ? 8u : 0u;
+      if (pre[i] == 0 && lens[i] && !datas[i]) return c->fail(HBX_ERR_ARG, "null block data");
+      file[i] = (uint32_t)f;
+      bool h = false;
+      caps[i] = pre[i] ? 0 : many_cap(mb, size_hint, f, types[i], lens[i], &h);
+      hinted[i] = h ? 1 : 0;
+    }
+  // gather: a file's bytes go to out + (the good bytes of the files before it) + its own offset
+  std::vector<uint64_t> fbase(n_files + 1, 0);
+  uint64_t done_files = 0;  // fbase[0 .. done_files] is final
+  auto settle = [&](uint64_t upto) {  // every file before `upto` has all its blocks behind it
+    for (; done_files < upto; done_files++) fbase[done_files + 1] = fbase[done_files] + R.run[done_files];
+  };
+  R.emit = [&](const std::vector<ManySeg>& segs, const uint8_t* image) -> int {
+    for (const ManySeg& sg : segs) {
+      if (sg.was_bad || sg.good == 0) continue;
+      settle(sg.file);
+      if (fbase[sg.file] + sg.foff0 + sg.good > out_cap)
+        return c->fail(HBX_ERR_CAPACITY, "out_cap is smaller than the restored prefixes");
+      std::memcpy(out + fbase[sg.file] + sg.foff0, image + sg.img, sg.good);
+    }
+    return HBX_OK;
+  };
+  R.local = [&](std::vector<ManySeg>& segs, const uint8_t** host, uint64_t* total) -> int {
+    uint64_t pos = 0;
+    for (ManySeg& sg : segs) {
+      const uint64_t llen = local_offs[sg.file + 1] - local_offs[sg.file];
+      sg.have = (sg.was_bad || llen <= sg.foff0) ? 0 : std::min(sg.bytes, llen - sg.foff0);
+      sg.loff = pos;
+      pos += sg.have;
+    }
+    HBX_TRY(c, c->h_rout[0].ensure(pos + 64));
+    uint8_t* h = c->h_rout[0].as<uint8_t>();
+    for (const ManySeg& sg : segs)
+      if (sg.have) std::memcpy(h + sg.loff, local + local_offs[sg.file] + sg.foff0, sg.have);
+    *host = h;
+    *total = pos;
+    return HBX_OK;
+  };
+  ManyStaged S;
+  for (uint64_t a = 0; a < n;) {
+    uint64_t b = many_window_end(n, caps.data(), R.wb, a);
+    // stage the data fields through pinned memory, one copy per window: zlib streams at 16-byte
+    // boundaries (K8's vector loads), raw blocks packed byte by byte behind whatever precedes them
+    const auto t_stage = std::chrono::steady_clock::now();
+    const uint64_t room = many_stage_cap(R.wb, in_slot);
+    S.clear(a);
+    uint64_t pos = 0;
+    std::vector<uint64_t> at;
+    for (uint64_t i = a; i < b; i++) {
+      if (pre[i] == 0 && types[i] == HBX_BLOCK_ZLIB) pos = (pos + 15) & ~15ull;
+      at.push_back(pos);
+      if (pre[i] == 0) pos += lens[i];
+      if (pos + 16 + bound > room) b = i + 1;  // the staging is full: the window ends here
+    }
+    HBX_TRY(c, c->h_rin[0].ensure(pos + 64));
+    HBX_TRY(c, c->d_rin[0].ensure(pos + 65536));
+    uint8_t* hin = c->h_rin[0].as<uint8_t>();
+    const uint64_t din = reinterpret_cast<uint64_t>(c->d_rin[0].p);
+    for (uint64_t i = a; i < b; i++) {
+      if (pre[i] == 0 && lens[i]) std::memcpy(hin + at[i - a], datas[i], lens[i]);
+      S.push(din + at[i - a], pre[i] ? 0 : lens[i], caps[i], types[i], hinted[i] != 0, pre[i], file[i]);
+    }
+    if (pos) HBX_TRY(c, hipMemcpyAsync(c->d_rin[0].p, hin, pos, hipMemcpyHostToDevice, c->stream));
+    HBX_TRY(c, hipStreamSynchronize(c->stream));
+    c->restore_ms[0] += ms_since(t_stage);
+    if (int rc = many_process(c, R, S)) return rc;
+    a = b;
+  }
+  settle(n_files);
+  for (uint64_t f = 0; f < n_files; f++) {
+    n_good[f] = R.ngood[f];
+    if (out_offs) out_offs[f + 1] = fbase[f + 1];
+    if (local) {
+      const uint64_t llen = local_offs[f + 1] - local_offs[f];
+      first_diff[f] = R.found[f] != hbxr::kNoDiff ? R.found[f]
+                      : llen != R.run[f]          ? std::min(llen, R.run[f])
+                                                  : hbxr::kNoDiff;
+    }
+  }
+  return HBX_OK;
+}
+
+int hbx_restore_files_stream(hbx_ctx* c, uint64_t n_files, const uint64_t* first, const uint8_t* ids,
+                             hbx_file_block_source_fn source, void* user, const uint64_t* size_hint,
+                             uint64_t window_bytes, const char* const* out_paths, const char* const* local_paths,
+                             uint32_t io_threads, uint64_t max_block, hbx_restored_file* results) {
+  if (!c || (n_files && (!first || !results))) return HBX_ERR_ARG;
+  if (n_files && (out_paths != nullptr) == (local_paths != nullptr)) return HBX_ERR_ARG;  // exactly one target
+  if (!many_first_ok(n_files, first)) return HBX_ERR_ARG;
+  const uint64_t n = n_files ? first[n_files] : 0;
+  if (n && (!ids || !source)) return HBX_ERR_ARG;
+  const uint64_t mb = restore_mb(max_block);
+  if (mb > kRestoreMaxBlock || n_files > 0x7FFFFFFFull || io_threads > 16) return HBX_ERR_ARG;
+  const char* const* paths = out_paths ? out_paths : local_paths;
+  for (uint64_t f = 0; f < n_files; f++)
+    if (!paths[f]) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  for (double& t : c->restore_ms) t = 0.0;
+  c->many_windows = c->many_passes = c->many_retries = 0;
+  const uint32_t threads = io_threads ? io_threads : 16u;
+  const bool diff = local_paths != nullptr;
+  for (uint64_t f = 0; f < n_files; f++) {
+    hbx_restored_file& r = results[f];
+    r.bytes = r.n_good = 0;
+    r.bad_index = r.first_diff = ~0ull;
+    r.bad_status = 0;
+    r.err = 0;
+  }
+  const uint64_t bound = hbx_restore_in_bound(mb), in_slot = (bound + 15) & ~15ull;
+  const uint64_t wb = window_bytes ? window_bytes : kManyWindow;
+  const uint64_t room = many_stage_cap(wb, in_slot);
+  // every buffer is sized by the window and max_block, never by the set of files
+  for (int k = 0; k < 2; k++) {
+    HBX_TRY(c, c->h_rin[k].ensure(room + 64));
+    HBX_TRY(c, c->d_rin[k].ensure(room + 65536));
+    HBX_TRY(c, c->h_rout[k].ensure(kImageLead + wb + mb + kImageGuard));
+  }
+  if (!c->fstream) HBX_TRY(c, hipStreamCreateWithFlags(&c->fstream, hipStreamNonBlocking));
+  ManyRun R;
+  R.mb = mb;
+  R.wb = wb;
+  R.expect = ids;
+  R.diff = diff;
+  R.init(n_files);
+  std::vector<uint64_t> local_len(diff ? n_files : 0, 0);
+  std::vector<uint8_t> sized(diff ? n_files : 0, 0);
+  auto note = [&](uint64_t f, int e) {  // the first error of a file stays
+    if (results[f].err == 0) results[f].err = e ? e : EIO;
+  };
+  auto size_local = [&](uint64_t f) {
+    int fd = ::open(local_paths[f], O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return note(f, errno);
+    const off_t end = ::lseek(fd, 0, SEEK_END);
+    if (end < 0) note(f, errno);
+    else local_len[f] = (uint64_t)end;
+    ::close(fd);
+  };
+  // files without blocks: created empty, or sized for the diff's length rule
+  {
+    std::vector<uint64_t> empty;
+    for (uint64_t f = 0; f < n_files; f++)
+      if (first[f] == first[f + 1]) empty.push_back(f);
+    many_pool(threads, empty.size(), [&](uint64_t j) {
+      const uint64_t f = empty[j];
+      if (diff) {
+        sized[f] = 1;
+        return size_local(f);
+      }
+      const int fd = ::open(out_paths[f], O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+      if (fd < 0 || ::close(fd) != 0) note(f, errno);
+    });
+  }
+  // diff: size the local copies met for the first time, then read the compared ranges into pinned memory
+  R.local = [&](std::vector<ManySeg>& segs, const uint8_t** host, uint64_t* total) -> int {
+    std::vector<uint64_t> fresh;
+    for (uint64_t k = 0; k < segs.size(); k++)
+      if (!sized[segs[k].file]) {
+        sized[segs[k].file] = 1;
+        fresh.push_back(segs[k].file);
+      }
+    many_pool(threads, fresh.size(), [&](uint64_t j) { size_local(fresh[j]); });
+    uint64_t pos = 0;
+    for (ManySeg& sg : segs) {
+      const uint64_t llen = local_len[sg.file];
+      sg.have = (sg.was_bad || results[sg.file].err || llen <= sg.foff0) ? 0 : std::min(sg.bytes, llen - sg.foff0);
+      sg.loff = pos;
+      pos += sg.have;
+    }
+    HBX_TRY(c, c->h_rout[0].ensure(pos + 64));
+    uint8_t* h = c->h_rout[0].as<uint8_t>();
+    many_pool(threads, segs.size(), [&](uint64_t k) {
+      const ManySeg& sg = segs[k];
+      if (!sg.have) return;
+      const int fd = ::open(local_paths[sg.file], O_RDONLY | O_CLOEXEC);
+      if (fd < 0) {
+        std::memset(h + sg.loff, 0, sg.have);
+        return note(sg.file, errno);
+      }
+      for (uint64_t done = 0; done < sg.have;) {
+        const ssize_t r = ::pread(fd, h + sg.loff + done, sg.have - done, (off_t)(sg.foff0 + done));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {  // the file shrank under the call
+          std::memset(h + sg.loff + done, 0, sg.have - done);
+          note(sg.file, r < 0 ? errno : EIO);
+          break;
+        }
+        done += (uint64_t)r;
+      }
+      ::close(fd);
+    });
+    *host = h;
+    *total = pos;
+    return HBX_OK;
+  };
+  // gather: the pool writes pass p's good prefixes from its pinned image while pass p + 1 runs
+  std::future<void> writing;
+  R.emit = [&](const std::vector<ManySeg>& segs, const uint8_t* image) -> int {
+    if (writing.valid()) writing.get();
+    writing = std::async(std::launch::async, [&, segs, image] {
+      many_pool(threads, segs.size(), [&](uint64_t k) {
+        const ManySeg& sg = segs[k];
+        if (sg.was_bad || results[sg.file].err) return;
+        const int fd = ::open(out_paths[sg.file], O_WRONLY | O_CLOEXEC | (sg.foff0 == 0 ? O_CREAT | O_TRUNC : 0), 0666);
+        if (fd < 0) return note(sg.file, errno);
+        for (uint64_t done = 0; done < sg.good;) {
+          const ssize_t r = ::pwrite(fd, image + sg.img + done, sg.good - done, (off_t)(sg.foff0 + done));
+          if (r < 0 && errno == EINTR) continue;
+          if (r <= 0) {
+            note(sg.file, r < 0 ? errno : EIO);
+            break;
+          }
+          done += (uint64_t)r;
+        }
+        if (::close(fd) != 0) note(sg.file, errno);
+      });
+    });
+    return HBX_OK;
+  };
+  // the fill thread: one source call at a time in (file, index) order into window k's pinned staging;
+  // a block that no longer fits the window waits in `carry` for the next one
+  ManyStaged fill[2];
+  struct Carry {
+    bool valid = false;
+    uint64_t len = 0;
+    uint8_t type = 0;
+    std::vector<uint8_t> data;
+  } carry;
+  uint64_t next_blk = 0, next_file = 0;
+  auto do_fill = [&](uint64_t k) -> int {
+    ManyStaged& F = fill[k & 1];
+    F.clear(next_blk);
+    if (hipSetDevice(c->device) != hipSuccess) {
+      F.err = "hipSetDevice failed on the fill thread";
+      return HBX_ERR_HIP;
+    }
+    uint8_t* h = c->h_rin[k & 1].as<uint8_t>();
+    const uint64_t d = reinterpret_cast<uint64_t>(c->d_rin[k & 1].p);
+    uint64_t pos = 0, sum = 0;
+    while (next_blk < n) {
+      while (first[next_file + 1] <= next_blk) next_file++;
+      pos = (pos + 15) & ~15ull;
+      uint64_t len = 0;
+      uint8_t type = 0;
+      if (carry.valid) {
+        len = carry.len;
+        type = carry.type;
+        if (len <= bound && len) std::memcpy(h + pos, carry.data.data(), len);
+        carry.valid = false;
+      } else if (source(user, next_file, next_blk - first[next_file], h + pos, bound, &len, &type) != 0) {
+        F.err = "the block source failed at block " + std::to_string(next_blk - first[next_file]) + " of file " +
+                std::to_string(next_file);
+        return HBX_ERR_IO;
+      }
+      const bool bad = len > bound || (type != HBX_BLOCK_RAW && type != HBX_BLOCK_ZLIB);
+      bool hinted = false;
+      const uint64_t cap = bad ? 0 : many_cap(mb, size_hint, next_file, type, len, &hinted);
+      const uint64_t share = many_slot(cap);
+      if (F.n && (share > wb || sum > wb - share)) {  // hbx_restore_many_window's rule: the next window's first block
+        carry.valid = true;
+        carry.len = len;
+        carry.type = type;
+        if (!bad) carry.data.assign(h + pos, h + pos + len);
+        break;
+      }
+      sum += share;
+      F.push(d + pos, bad ? 0 : len, cap, type, hinted, bad ? 8u : 0u, (uint32_t)next_file);
+      if (!bad) pos += len;
+      next_blk++;
+      if (pos + 16 + bound > room) break;  // the staging is full
+    }
+    F.last = next_blk >= n && !carry.valid;
+    hipError_t e = pos ? hipMemcpyAsync(c->d_rin[k & 1].p, h, pos, hipMemcpyHostToDevice, c->fstream) : hipSuccess;
+    if (e == hipSuccess) e = hipStreamSynchronize(c->fstream);
+    if (e != hipSuccess) {
+      F.err = std::string("restore input copy: ") + hipGetErrorString(e);
+      return HBX_ERR_HIP;
+    }
+    return HBX_OK;
+  };
+  int rc = HBX_OK;
+  std::future<int> filling;
+  if (n) filling = std::async(std::launch::async, do_fill, (uint64_t)0);
+  for (uint64_t k = 0; n && rc == HBX_OK; k++) {
+    rc = filling.get();
+    ManyStaged& F = fill[k & 1];
+    if (rc) {
+      c->err = F.err;
+      break;
+    }
+    const bool last = F.last;
+    if (!last) filling = std::async(std::launch::async, do_fill, k + 1);
+    rc = many_process(c, R, F);
+    if (last) break;
+  }
+  // drain: nothing of this call stays in flight, whatever happened
+  if (filling.valid()) (void)filling.get();
+  if (writing.valid()) writing.get();
+  for (hipStream_t s : {c->stream, c->rstream, c->fstream}) (void)hipStreamSynchronize(s);
+  for (uint64_t f = 0; f < n_files; f++) {
+    hbx_restored_file& r = results[f];
+    r.bytes = R.run[f];
+    r.n_good = R.ngood[f];
+    if (R.bad[f]) {
+      r.bad_index = R.ngood[f];
+      r.bad_status = R.bad_status[f];
+    }
+    if (diff && rc == HBX_OK && r.err == 0)
+      r.first_diff = R.found[f] != hbxr::kNoDiff ? R.found[f]
+                     : local_len[f] != R.run[f]  ? std::min(local_len[f], R.run[f])
+                                                 : hbxr::kNoDiff;
+  }
   return rc;
 }
 

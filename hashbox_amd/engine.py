@@ -67,6 +67,28 @@ class RestoredBlocks:
     first_diff: Optional[int]  # diff mode: first differing offset, None when nothing differs
 
 
+@dataclass(slots=True)
+class RestoredFiles:
+    """What :meth:`Engine.restore_files_blocks` returns (hbx_restore_files_blocks)."""
+    data: Optional[List[bytes]]  # per file: its bytes up to its first bad block; None in diff mode
+    out_offs: np.ndarray  # uint64 [n_files + 1]: where each file's bytes lie in the packed image
+    blk_offs: List[np.ndarray]  # per file, uint64 per block: its offset inside the file (2**64 - 1 once bad)
+    status: List[np.ndarray]  # per file, uint32 per block: as RestoredBlocks.status
+    n_good: np.ndarray  # int64 [n_files]: leading blocks with status 0
+    first_diff: Optional[List[Optional[int]]]  # diff mode, per file: first differing offset, None when equal
+
+
+@dataclass(slots=True)
+class RestoredFile:
+    """One file's result of :meth:`Engine.restore_files` (hbx_restored_file)."""
+    bytes: int  # the bytes of its good prefix
+    n_good: int  # its leading good blocks
+    bad_index: Optional[int]  # the index of its first bad block, None if every block is good
+    bad_status: int
+    errno: int  # of a path that could not be created, written, opened or read; else 0
+    first_diff: Optional[int] = None  # diff mode
+
+
 def max_chunks(n: int) -> int:
     return n // MIN_BLOCK_SIZE + 1
 
@@ -843,6 +865,171 @@ class Engine:
         when one side only ends early), None when the two are equal."""
         _, first = self._restore_stream(ids, source, None, None, local_path, window_bytes, max_block)
         return (True, None) if first == _lib.NO_DIFF else (False, first)
+
+    # ------------------------------------------- restore / diff, many files --
+    def restore_files_blocks(self, chains: Sequence[Sequence[tuple]], size_hints: Optional[Sequence[int]] = None,
+                             local: Optional[Sequence[BytesLike]] = None, max_block: Optional[int] = None,
+                             out: Optional[np.ndarray] = None) -> RestoredFiles:
+        """restoreFileData / diffFileData over the chains of many files in one
+        call (hashback/restore.go:45-66, 137-162, 249-277;
+        hbx_restore_files_blocks): ``chains[f]`` lists file f's blocks in order
+        as ``(type, data field, id[, links])``.  A directory or chain block is
+        a one-block file with its links.  Windows are formed across files; the
+        prefix rule holds per file.  ``size_hints[f]`` (FileEntry.FileSize, 0 =
+        unknown) sizes the inflate slots and changes no result.  With ``local``
+        (one local copy per file) nothing is assembled and ``first_diff[f]`` is
+        the first offset at which file f differs."""
+        nf = len(chains)
+        first = np.zeros(nf + 1, np.uint64)
+        first[1:] = np.cumsum([len(ch) for ch in chains], dtype=np.uint64)
+        blocks = [b for ch in chains for b in ch]
+        n = len(blocks)
+        arrs = [_u8(b[1]) for b in blocks]
+        ida = _ids_array([b[2] for b in blocks])
+        ty = np.array([int(b[0]) for b in blocks], np.uint8)
+        lens = np.array([a.size for a in arrs], np.uint64)
+        ptrs = np.array([_p(a) for a in arrs], np.uint64)
+        links_a, base, counts = self._links_arrays([list(b[3]) if len(b) > 3 and b[3] else [] for b in blocks], n)
+        mb = int(max_block) if max_block else _lib.MAX_BLOCK
+        hints = None
+        if size_hints is not None:
+            hints = np.ascontiguousarray(size_hints, np.uint64)
+            if hints.size != nf:
+                raise ValueError("one size hint per file")
+        blk_offs = np.zeros(max(n, 1), np.uint64)
+        status = np.zeros(max(n, 1), np.uint32)
+        n_good = np.zeros(max(nf, 1), np.uint64)
+        first_diff = np.zeros(max(nf, 1), np.uint64)
+        out_offs = np.zeros(nf + 1, np.uint64)
+        loc = loc_offs = None
+        if local is not None:
+            if out is not None:
+                raise ValueError("out and local exclude each other")
+            if len(local) != nf:
+                raise ValueError("one local copy per file")
+            la = [_u8(x) for x in local]
+            loc_offs = np.zeros(nf + 1, np.uint64)
+            loc_offs[1:] = np.cumsum([a.size for a in la], dtype=np.uint64)
+            loc = np.concatenate(la + [np.zeros(1, np.uint8)])  # never NULL: that would mean "no local copy"
+
+        def call(o):
+            return self._L.hbx_restore_files_blocks(
+                self._ctx, nf, _p(first), _p(ptrs), _p(lens), _p(ty), _p(ida),
+                _p(links_a) if links_a is not None else None, _p(base) if base is not None else None,
+                _p(counts) if counts is not None else None, _p(hints) if hints is not None else None,
+                int(max_block or 0), ctypes.c_void_p(o.ctypes.data) if o is not None else None,
+                int(o.size) if o is not None else 0, _p(out_offs),
+                ctypes.c_void_p(loc.ctypes.data) if loc is not None else None,
+                _p(loc_offs) if loc_offs is not None else None, _p(blk_offs), _p(status), _p(n_good), _p(first_diff))
+
+        def bound(hinted):  # an upper bound of the packed image: deflate expands at most 1032-fold
+            tot = 0
+            for f in range(nf):
+                h = int(hints[f]) if hinted and hints is not None else 0
+                for i in range(int(first[f]), int(first[f + 1])):
+                    k = int(lens[i])
+                    tot += k if ty[i] == _lib.BLOCK_RAW else min(mb, h or 1032 * k + 64)
+            return max(tot, 1)
+
+        if loc is not None:
+            rc = call(None)
+        elif out is not None:
+            rc = call(out)
+        else:
+            out = np.empty(bound(True), np.uint8)
+            rc = call(out)
+            if rc == _lib.ERR_CAPACITY and hints is not None:  # a hint was too small: it is never trusted
+                out = np.empty(bound(False), np.uint8)
+                rc = call(out)
+        self._check(rc, "hbx_restore_files_blocks")
+        fo = [int(x) for x in first]
+        data = fds = None
+        if loc is None:
+            oo = [int(x) for x in out_offs]
+            data = [out[oo[f]:oo[f + 1]].tobytes() for f in range(nf)]
+        else:
+            fds = [None if int(x) == _lib.NO_DIFF else int(x) for x in first_diff[:nf]]
+        return RestoredFiles(data, out_offs, [blk_offs[fo[f]:fo[f + 1]].copy() for f in range(nf)],
+                             [status[fo[f]:fo[f + 1]].copy() for f in range(nf)], n_good[:nf].astype(np.int64), fds)
+
+    def _restore_files_stream(self, chains_ids, source, out_paths, local_paths, size_hints, window_bytes: int,
+                              io_threads: int, max_block) -> List[RestoredFile]:
+        nf = len(chains_ids)
+        first = np.zeros(nf + 1, np.uint64)
+        first[1:] = np.cumsum([len(ch) for ch in chains_ids], dtype=np.uint64)
+        ida = _ids_array([i for ch in chains_ids for i in ch])
+        paths = out_paths if out_paths is not None else local_paths
+        if len(paths) != nf:
+            raise ValueError("one path per file")
+        enc = [os.fsencode(p) for p in paths]
+        parr = (ctypes.c_char_p * max(nf, 1))(*enc)
+        hints = None
+        if size_hints is not None:
+            hints = np.ascontiguousarray(size_hints, np.uint64)
+            if hints.size != nf:
+                raise ValueError("one size hint per file")
+        raised = []
+
+        def src(_user, f, index, dst, cap, plen, ptype):
+            try:
+                t, data = source(int(f), int(index))
+                a = _u8(data)
+                plen[0] = a.size
+                ptype[0] = int(t)
+                if 0 < a.size <= cap:
+                    ctypes.memmove(dst, a.ctypes.data, a.size)
+                return 0
+            except BaseException as e:  # never unwind through C: a non-zero return, re-raised below
+                raised.append(e)
+                return 1
+
+        cb = _lib.FILE_BLOCK_SOURCE(src)
+        res = (_lib.RestoredFile * max(nf, 1))()
+        t0 = time.perf_counter()
+        rc = self._L.hbx_restore_files_stream(
+            self._ctx, nf, _p(first), _p(ida), ctypes.cast(cb, ctypes.c_void_p), None,
+            _p(hints) if hints is not None else None, int(window_bytes),
+            parr if out_paths is not None else None, parr if local_paths is not None else None,
+            int(io_threads), int(max_block or 0), res)
+        self.last_call_s = time.perf_counter() - t0
+        if raised:
+            raise raised[0]
+        if rc == _lib.ERR_IO:
+            msg = self._L.hbx_last_error(self._ctx)
+            raise RestoreError(f"hbx_restore_files_stream: HBX_ERR_IO: {msg.decode() if msg else ''}", rc, None, 0,
+                               sum(int(res[f].bytes) for f in range(nf)))
+        self._check(rc, "hbx_restore_files_stream")
+        return [RestoredFile(int(r.bytes), int(r.n_good), None if r.bad_index == _lib.NO_DIFF else int(r.bad_index),
+                             int(r.bad_status), int(r.err), None if r.first_diff == _lib.NO_DIFF else int(r.first_diff))
+                for r in res[:nf]]
+
+    def restore_files(self, chains_ids, source: Callable[[int, int], tuple], out_paths, size_hints=None,
+                      window_bytes: int = 0, io_threads: int = 16, max_block: Optional[int] = None
+                      ) -> List[RestoredFile]:
+        """restoreFileData for many files in one call (restore.go:45-66,
+        137-162; hbx_restore_files_stream): ``chains_ids[f]`` lists the block
+        IDs of file f, ``source(f, i)`` returns its block i as ``(type, data
+        field)``, ``out_paths[f]`` is created or truncated and receives the
+        file's good prefix.  Windows hold blocks of many files, two in flight;
+        ``io_threads`` (at most 16) writers.  Returns one :class:`RestoredFile`
+        per file: a bad block (``bad_index``, ``bad_status``) or a path that
+        cannot be written (``errno``) is that file's result and the others
+        complete.  A failing source raises (:class:`RestoreError` with
+        ``code == _lib.ERR_IO``, or the exception ``source`` raised)."""
+        return self._restore_files_stream(chains_ids, source, out_paths, None, size_hints, window_bytes, io_threads,
+                                          max_block)
+
+    def diff_files(self, chains_ids, source: Callable[[int, int], tuple], local_paths, size_hints=None,
+                   window_bytes: int = 0, io_threads: int = 16, max_block: Optional[int] = None):
+        """diffFileData for many files in one call (restore.go:249-277,
+        279-414): returns one ``(same, first_diff)`` per file, ``first_diff``
+        the first differing offset inside the file (the shorter length when one
+        side only ends early), None when the two are equal.  A file with a bad
+        block is never the same (its good prefix is what was compared); a local
+        copy that cannot be read is ``(False, None)``."""
+        res = self._restore_files_stream(chains_ids, source, None, local_paths, size_hints, window_bytes, io_threads,
+                                         max_block)
+        return [(r.first_diff is None and r.bad_index is None and r.errno == 0, r.first_diff) for r in res]
 
     def memcpy_h2d_async(self, d_dst: int, h_src: int, nbytes: int):
         """Enqueue an H2D copy on this engine's stream (pinned source)."""

@@ -331,10 +331,113 @@ def _read_verified(eng: Engine, read_block, block_id: bytes, what: str) -> bytes
     return r.data
 
 
-def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_bytes: int = 0) -> Dict[str, int]:
+def _read_verified_many(eng: Engine, read_block, ids: Sequence[bytes], what: str) -> List[bytes]:
+    """ReadBlock + VerifyBlock of many directory or chain blocks in one device
+    call (Engine.restore_files_blocks, each block a one-block file with its
+    links).  The first bad one raises."""
+    if not ids:
+        return []
+    chains = []
+    for bid in ids:
+        btype, data, links = read_block(bytes(bid))
+        chains.append([(btype, data, bytes(bid), list(links or []))])
+    r = eng.restore_files_blocks(chains)
+    for k, bid in enumerate(ids):
+        if int(r.n_good[k]) != 1:
+            raise HbxError(f"{what} block {bytes(bid).hex()} corrupted (status {int(r.status[k][0])})")
+    return r.data
+
+
+def _file_chains(eng: Engine, read_block, entries: Sequence[FileEntry]) -> List[List[bytes]]:
+    """The data block IDs of every file entry: its FileChainBlock's list (all
+    chain blocks read and verified in one call) or its one ContentBlockID."""
+    chained = [k for k, e in enumerate(entries) if e.content_type == TYPE_FILE_CHAIN]
+    blocks = _read_verified_many(eng, read_block, [entries[k].content_block_id for k in chained], "chain")
+    ids: List[List[bytes]] = [[bytes(e.content_block_id)] if e.content_type == TYPE_FILE_DATA else [] for e in entries]
+    for k, blk in zip(chained, blocks):
+        ids[k] = [bytes(i) for i in parse_chain_block(blk)[0]]
+    return ids
+
+
+def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: bytes, window_bytes: int,
+                          io_threads: int) -> Dict[str, int]:
+    stats = {"files": 0, "directories": 0, "bytes": 0}
+    made_dirs: List[Tuple[bytes, int]] = []
+    files: List[Tuple[FileEntry, bytes, int]] = []  # entry, local path, the mode its creation gave it
+    level: List[Tuple[FileEntry, bytes]] = [(root_entry, dest)]
+    while level:  # breadth-first: one device call per level of directory blocks
+        want: List[Tuple[FileEntry, bytes]] = []
+        for e, path in level:
+            local = os.path.join(path, bytes(e.file_name))
+            if e.file_mode & MODE_SYMLINK:  # restore.go:76-84
+                if e.content_type != TYPE_SYMLINK:
+                    raise HbxError(f"invalid ContentType for a symlink ({e.content_type})")
+                os.symlink(bytes(e.file_link), local)
+            elif e.file_mode & MODE_DIR:  # restore.go:85-102
+                os.makedirs(local, 0o777, exist_ok=True)
+                if e.content_type == TYPE_DIRECTORY:
+                    want.append((e, local))
+                elif e.content_type != TYPE_EMPTY:
+                    raise HbxError(f"invalid ContentType for a directory ({e.content_type})")
+                made_dirs.append((local, e.file_mode & 0o777))
+                stats["directories"] += 1
+            else:  # restore.go:103-145
+                if e.content_type not in (TYPE_FILE_CHAIN, TYPE_FILE_DATA, TYPE_EMPTY):
+                    raise HbxError(f"invalid ContentType for a file ({e.content_type})")
+                fd = os.open(local, os.O_CREAT | os.O_TRUNC | os.O_WRONLY, e.file_mode & 0o777)
+                mode = stat.S_IMODE(os.fstat(fd).st_mode)
+                os.close(fd)
+                files.append((e, local, mode))
+        blocks = _read_verified_many(eng, read_block, [e.content_block_id for e, _ in want], "directory")
+        level = [(kid, local) for (_, local), blk in zip(want, blocks) for kid in parse_directory_block(blk)]
+    ids = _file_chains(eng, read_block, [e for e, _, _ in files])
+    with_data = [k for k in range(len(files)) if ids[k]]
+    # (a mode without the owner's write bit, 0444: writable while written, as in the unbatched path)
+    locked = [k for k in with_data if not files[k][2] & stat.S_IWUSR]
+    for k in locked:
+        os.chmod(files[k][1], files[k][2] | stat.S_IWUSR)
+    try:
+        res = eng.restore_files([ids[k] for k in with_data], lambda f, i: read_block(ids[with_data[f]][i])[:2],
+                                [files[k][1] for k in with_data],
+                                size_hints=[max(int(files[k][0].file_size), 0) for k in with_data],
+                                window_bytes=window_bytes, io_threads=io_threads) if with_data else []
+    finally:
+        for k in locked:
+            os.chmod(files[k][1], files[k][2])
+    for k, r in zip(with_data, res):
+        if r.bad_index is not None:
+            raise HbxError(f"block {ids[k][r.bad_index].hex()} (block {r.bad_index} of {os.fsdecode(files[k][1])}) "
+                           f"corrupted (status {r.bad_status})")
+        if r.errno:
+            raise HbxError(f"cannot write {os.fsdecode(files[k][1])}: {os.strerror(r.errno)}")
+        stats["bytes"] += r.bytes
+    now = time.time_ns()
+    for e, local, _ in files:
+        os.utime(local, ns=(now, int(e.mod_time)))
+        stats["files"] += 1
+    for local, mode in reversed(made_dirs):  # after its content (restore.go:99), children before parents
+        os.chmod(local, mode)
+    return stats
+
+
+def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_bytes: int = 0,
+                 batch: bool = False, io_threads: int = 16) -> Dict[str, int]:
     """restoreEntry(root_entry, dest) (hashback/restore.go:68-162): the
     counterpart of :func:`store_tree`.  ``read_block(id)`` returns a block as
     it comes off the wire: ``(data type, data field, links)``.
+
+    With ``batch=True`` the tree is read breadth-first with a few device calls
+    instead of one round trip per block and per file: every directory block of
+    a level in one ``Engine.restore_files_blocks`` call, every chain block of
+    the tree's files in one more, and all file data through one
+    ``Engine.restore_files`` with the entries' FileSize as size hints.  Modes,
+    read-only files, symbolic links, empty files, ModTime and the directories'
+    chmod after their content are as below.  The difference: the unbatched
+    path stops at the first bad block in depth-first order and has written
+    nothing after it; the batched path raises :class:`HbxError` for the first
+    bad block in ITS order (directory blocks level by level, then chain blocks,
+    then data blocks in the order the files were met), and the good files of
+    the same batch have been written by then (without their ModTime).
 
     Directory blocks and chain blocks are inflated and verified on the device
     with their links (``Engine.restore_blocks``), then parsed
@@ -347,6 +450,8 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
     (restore.go:57).  Returns the counts ``{"files", "directories", "bytes"}``.
     """
     dest = os.fsencode(os.fspath(dest))
+    if batch:
+        return _restore_tree_batched(eng, root_entry, read_block, dest, window_bytes, io_threads)
     stats = {"files": 0, "directories": 0, "bytes": 0}
 
     def restore_entry(e: FileEntry, path: bytes):
@@ -392,3 +497,103 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
 
     restore_entry(root_entry, dest)
     return stats
+
+
+def diff_tree(eng: Engine, root_entry: FileEntry, read_block, local_root, window_bytes: int = 0,
+              io_threads: int = 16) -> Dict[str, object]:
+    """diffEntry(root_entry, local_root) with diffDir below it
+    (hashback/restore.go:279-414): compare a stored tree with a local one.
+
+    Per entry, as the reference: the local path exists; a symbolic link points
+    to the same target; a directory is a directory; a file has the same size,
+    permission bits and ModTime (at second precision).  The data of every file
+    whose size matches is compared on the device in one ``Engine.diff_files``
+    call (every block verified; a corrupted block raises :class:`HbxError`, as
+    the reference panics).  Directory and chain blocks are read level by level
+    in batched calls, as ``restore_tree(batch=True)`` does.  A name only one
+    side has is reported for the whole of both listings (the reference's merge
+    loop ends with the shorter one).  ``platformSafeFilename`` is not applied.
+
+    Returns ``{"files", "directories", "different"}``: the files and
+    directories compared, and one ``(path, reason)`` per path that differs.
+    """
+    root = os.fsencode(os.fspath(local_root))
+    reasons: Dict[bytes, List[str]] = {}
+    order: List[bytes] = []
+
+    def differs(path: bytes, why: str):
+        if path not in reasons:
+            reasons[path] = []
+            order.append(path)
+        reasons[path].append(why)
+
+    out = {"files": 0, "directories": 0}
+    data_files: List[Tuple[FileEntry, bytes]] = []
+    level: List[Tuple[FileEntry, bytes]] = [(root_entry, root)]
+    while level:
+        want: List[Tuple[FileEntry, bytes]] = []
+        for e, path in level:
+            local = os.path.join(path, bytes(e.file_name))
+            try:
+                st = os.lstat(local)
+            except FileNotFoundError:
+                differs(local, "local path does not exist")
+                continue
+            if e.file_mode & MODE_SYMLINK:  # restore.go:287-303
+                if e.content_type != TYPE_SYMLINK:
+                    raise HbxError(f"invalid ContentType for a symlink ({e.content_type})")
+                if not stat.S_ISLNK(st.st_mode):
+                    differs(local, "local path is not a symlink")
+                elif os.readlink(local) != bytes(e.file_link):
+                    differs(local, f"symlink points to {os.fsdecode(os.readlink(local))} and not "
+                                   f"{os.fsdecode(bytes(e.file_link))}")
+            elif e.file_mode & MODE_DIR:  # restore.go:304-316
+                if not stat.S_ISDIR(st.st_mode):
+                    differs(local, "local path is not a directory")
+                    continue
+                if e.content_type == TYPE_DIRECTORY:
+                    want.append((e, local))
+                elif e.content_type != TYPE_EMPTY:
+                    raise HbxError(f"invalid ContentType for a directory ({e.content_type})")
+                out["directories"] += 1
+            else:  # restore.go:317-367
+                if e.content_type not in (TYPE_FILE_CHAIN, TYPE_FILE_DATA, TYPE_EMPTY):
+                    raise HbxError(f"invalid ContentType for a file ({e.content_type})")
+                if not stat.S_ISREG(st.st_mode):
+                    differs(local, "local path is not a regular file")
+                    continue
+                if int(e.file_size) != st.st_size:
+                    differs(local, f"local file size {st.st_size} and remote size {int(e.file_size)} are different")
+                    continue
+                if e.file_mode & 0o777 != stat.S_IMODE(st.st_mode) & 0o777:
+                    differs(local, f"local permissions {stat.S_IMODE(st.st_mode) & 0o777:o} and remote "
+                                   f"{e.file_mode & 0o777:o} are different")
+                if int(e.mod_time) // 10**9 != st.st_mtime_ns // 10**9:
+                    differs(local, "local modification time and remote are different")
+                if e.content_type != TYPE_EMPTY:
+                    data_files.append((e, local))
+                out["files"] += 1
+        blocks = _read_verified_many(eng, read_block, [e.content_block_id for e, _ in want], "directory")
+        level = []
+        for (_, local), blk in zip(want, blocks):  # diffDir, restore.go:372-414
+            kids = parse_directory_block(blk)
+            remote = {bytes(k.file_name) for k in kids}
+            for name in sorted(os.listdir(local)):
+                if name not in remote:
+                    differs(os.path.join(local, name), "remote path does not exist")
+            level.extend((kid, local) for kid in kids)
+    ids = _file_chains(eng, read_block, [e for e, _ in data_files])
+    if data_files:
+        res = eng._restore_files_stream(ids, lambda f, i: read_block(ids[f][i])[:2], None,
+                                        [p for _, p in data_files],
+                                        [max(int(e.file_size), 0) for e, _ in data_files], window_bytes, io_threads, None)
+        for (e, local), r, chain in zip(data_files, res, ids):
+            if r.bad_index is not None:
+                raise HbxError(f"block {chain[r.bad_index].hex()} (block {r.bad_index} of {os.fsdecode(local)}) "
+                               f"corrupted (status {r.bad_status})")
+            if r.errno:
+                differs(local, f"cannot read the local file: {os.strerror(r.errno)}")
+            elif r.first_diff is not None:
+                differs(local, f"data is different at offset {r.first_diff}")
+    out["different"] = [(os.fsdecode(p), "; ".join(reasons[p])) for p in order]
+    return out

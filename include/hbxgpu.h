@@ -785,6 +785,101 @@ int hbx_restore_file_stream(hbx_ctx *ctx, uint64_t n_blocks, const uint8_t *ids,
                             const char *local_path, uint64_t max_block, uint64_t *bytes, uint64_t *bad_index,
                             uint32_t *bad_status, uint64_t *first_diff);
 
+/* ---- Restore and diff of many files in one call (K11) --------------------------
+ * restoreDir restores a directory's entries one after the other
+ * (hashback/restore.go:137-162: restoreEntry per FileEntry, restore.go:68-135,
+ * each file through restoreFileData, restore.go:45-66); diffDir / diffEntry
+ * walk the same way and compare (restore.go:279-414, diffFileData 249-277).
+ * The calls above take one chain per call, a round trip per file.  These are
+ * the read side's counterpart of hbx_store_paths: the chains of MANY files in
+ * one call, in WINDOWS formed across files, with a result per file.
+ *
+ * Blocks are listed in (file, index) order; file f owns the blocks
+ * [first[f], first[f + 1]) (first holds n_files + 1 entries, first[0] = 0).  A
+ * directory or chain block is a one-block "file" (links as hbx_verify_blocks).
+ * Per-block statuses are exactly hbx_restore_blocks' (0-8) and its PREFIX rule
+ * holds per file: file f's result is its n_good[f] leading good blocks,
+ * nothing of it past its first bad block is written, and a bad block in one
+ * file changes nothing in any other.  A corrupt block is a result: HBX_OK.
+ *
+ * Size hints (FileEntry.FileSize per file; NULL or 0 = unknown): a zlib block
+ * of file f gets an inflate slot of min(max_block, hint[f]) bytes instead of
+ * max_block, so a window holds thousands of small blocks and K8 can take its
+ * lane-per-stream mode.  A hint is never trusted: a stream that overflows a
+ * slot smaller than max_block is inflated again into a max_block slot while
+ * its window is staged, and fails (status 3) only if it overflows that too.
+ * Results are the same for every hint vector.
+ *
+ * hbx_restore_many_window is the window rule, pure host arithmetic: block i
+ * takes caps[i] rounded up to 256, + 256 slack, of the window (caps: a zlib
+ * block's slot capacity as above, a raw block's length, 0 for a status-8
+ * block); *end = the first block after `start` that no longer fits
+ * window_bytes (0 = 1 GiB), at least start + 1 (start == n: *end = n).  A
+ * window also ends where its staged data fields reach window_bytes +
+ * window_bytes / 512 + 2 hbx_restore_in_bound(max_block) + 4096 bytes (data
+ * fields far longer than their hinted capacity).  Each window: K8 / K8s, then
+ * K11 (hbx_k11_gather / hbx_k11_diff, a piece of at most 16 KiB per wave)
+ * beside VerifyBlock (K6), guard bytes on both sides of the packed image
+ * checked, every stream idle on return, also on failure.  When hints were
+ * wrong the window runs as several K11 passes, cut by the same rule over the
+ * corrected capacities. */
+int hbx_restore_many_window(uint64_t n, const uint64_t *caps, uint64_t window_bytes, uint64_t start, uint64_t *end);
+/* n_files chains in host memory (datas / lens / types / expect / links as
+ * hbx_restore_blocks, over all first[n_files] blocks).  Exactly one of out and
+ * local is set.  out: the PACKED image, file f's good prefix at
+ * out[out_offs[f] .. out_offs[f + 1]) (out_offs holds n_files + 1); an out_cap
+ * smaller than that is HBX_ERR_CAPACITY.  local (diff mode): the packed local
+ * copies, file f's at local[local_offs[f] .. local_offs[f + 1]); first_diff[f]
+ * is what hbx_restore_blocks defines, per file: the smallest offset inside the
+ * file's good prefix at which the two differ, else the shorter length if the
+ * lengths differ, else UINT64_MAX.  blk_offs (may be NULL) receives per block
+ * its offset inside its file (UINT64_MAX at and past the file's first bad
+ * block), status per block its status, n_good per file its leading good
+ * blocks.  Windows are 1 GiB.  Contradictory arguments return HBX_ERR_ARG
+ * before the context is touched; HBX_ERR_STATE while batches are pending.
+ * Synchronous. */
+int hbx_restore_files_blocks(hbx_ctx *ctx, uint64_t n_files, const uint64_t *first,
+                             const uint8_t *const *datas, const uint64_t *lens, const uint8_t *types,
+                             const uint8_t *expect, const uint8_t *links, const uint64_t *link_base,
+                             const uint32_t *n_links, const uint64_t *size_hint, uint64_t max_block,
+                             uint8_t *out, uint64_t out_cap, uint64_t *out_offs,
+                             const uint8_t *local, const uint64_t *local_offs,
+                             uint64_t *blk_offs, uint32_t *status, uint64_t *n_good, uint64_t *first_diff);
+/* Block `index` of file `file`, otherwise as hbx_block_source_fn. */
+typedef int (*hbx_file_block_source_fn)(void *user, uint64_t file, uint64_t index, uint8_t *dst, uint64_t cap,
+                                        uint64_t *len, uint8_t *type);
+typedef struct {
+  uint64_t bytes;      /* the bytes of the file's good prefix (restored or compared) */
+  uint64_t n_good;     /* its leading good blocks */
+  uint64_t bad_index;  /* the index in the file of its first bad block, UINT64_MAX if none */
+  uint64_t first_diff; /* diff mode, as hbx_restore_files_blocks; UINT64_MAX also when err != 0 */
+  uint32_t bad_status; /* that block's status */
+  int32_t err;         /* errno of a path that could not be created, written, opened or read; else 0 */
+} hbx_restored_file;
+/* The same for files of any number and size, two windows in flight as in
+ * hbx_restore_file_stream: a fill thread calls src one call at a time in
+ * (file, index) order into pinned staging (ids: the expected BlockIDs in the
+ * same order); a pool of io_threads writers (0 = 16; more than 16 is
+ * HBX_ERR_ARG) creates or truncates out_paths[f] and pwrites the file's good
+ * prefix, a file that spans windows at its running offset; a file without
+ * blocks is created empty.  With local_paths instead (diff mode; exactly one
+ * of the two is set) the pool reads the local files and nothing is written.
+ * A path that cannot be created, written, opened or read is that file's err
+ * and the call goes on; a bad block is that file's bad_index / bad_status and
+ * the call goes on (HBX_OK).  A failing src is HBX_ERR_IO.  After any failure
+ * the streams are drained and the context is usable.
+ * Memory depends on window_bytes (W; 0 = 1 GiB) and max_block (M) only.  With
+ * S = W + W / 512 + 2 hbx_restore_in_bound(M) + 4096: device 2 S of staged
+ * input + W of slots + max(W, M + 512) of slots for streams inflated again
+ * (+ W + M in diff mode); pinned host 2 S + 2 (W + M) (about 4.1 GiB pinned at
+ * the defaults).  The buffers are kept for the next call and freed by
+ * hbx_ctx_destroy.  Synchronous; HBX_ERR_STATE while batches are pending;
+ * contradictory arguments return HBX_ERR_ARG before the context is touched. */
+int hbx_restore_files_stream(hbx_ctx *ctx, uint64_t n_files, const uint64_t *first, const uint8_t *ids,
+                             hbx_file_block_source_fn src, void *user, const uint64_t *size_hint,
+                             uint64_t window_bytes, const char *const *out_paths, const char *const *local_paths,
+                             uint32_t io_threads, uint64_t max_block, hbx_restored_file *results);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
@@ -812,8 +907,9 @@ int hbx_free_pinned(void *p);
  * and whether the HBX_* A/B environment switches were honoured (ab_env: they
  * are read only when HBX_AB=1); restore_ms: the host milliseconds the latest
  * hbx_restore_* call spent staging its input, inflating, verifying beside
- * K10, and copying out, each phase ending on a synchronization.  No reference
- * counterpart: diagnostics. */
+ * K10 / K11, and copying out, each phase ending on a synchronization;
+ * restore_many: the staged windows, K11 passes and streams inflated again of
+ * the latest hbx_restore_files_* call.  No reference counterpart: diagnostics. */
 int hbx_knobs(hbx_ctx *ctx, char *out, uint64_t cap);
 
 /* Device time (ms) of the last completed batch per stage:
