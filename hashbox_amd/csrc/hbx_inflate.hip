@@ -46,10 +46,11 @@ __device__ const uint8_t kOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 
 
 // The code of `n` symbols with code lengths `lens` (RFC 1951 §3.2.2 steps
 // 1-3: count per length, first code per length, symbols in code order).
-// Returns false when the lengths over-subscribe the code space; incomplete
-// codes are accepted (a decoder meets a missing code only on corrupt input),
-// and all-zero lengths give a code that decodes nothing.
-__device__ __forceinline__ bool construct(Code& c, uint16_t* sym, uint16_t* next, const uint8_t* lens, int n) {
+// Returns the code space left unused, in 15-bit codes: 0 for a complete
+// code, 32768 for all-zero lengths (a code that decodes nothing), and -1
+// when the lengths over-subscribe the code space.  What an incomplete code
+// is worth is the caller's decision (code_usable below).
+__device__ __forceinline__ int construct(Code& c, uint16_t* sym, uint16_t* next, const uint8_t* lens, int n) {
   uint16_t count[16];
   for (int l = 0; l < 16; l++) count[l] = 0;
   for (int s = 0; s < n; s++) count[lens[s]]++;
@@ -60,7 +61,7 @@ __device__ __forceinline__ bool construct(Code& c, uint16_t* sym, uint16_t* next
   c.base[0] = 0;
   for (int l = 1; l < 16; l++) {
     room = 2 * room - count[l];
-    if (room < 0) return false;
+    if (room < 0) return -1;
     first = (first + count[l - 1]) << 1;
     c.limit[l] = (uint16_t)(first + count[l]);
     c.base[l] = (int16_t)((int)start - (int)first);
@@ -69,7 +70,19 @@ __device__ __forceinline__ bool construct(Code& c, uint16_t* sym, uint16_t* next
   }
   for (int s = 0; s < n; s++)
     if (lens[s]) sym[next[lens[s]]++] = (uint16_t)s;
-  return true;
+  return room;
+}
+
+// May a block use the code `c` that construct() left `left` code space in?
+// The rule of zlib's inflate_table and of Go's huffmanDecoder.init: a
+// literal/length or distance code must be complete, unless it is a single
+// code of length 1; a distance code may also be empty (a block of literals
+// only).  The code-length code (strict) must be complete.
+__device__ __forceinline__ bool code_usable(int left, const Code& c, bool strict, bool may_be_empty) {
+  if (left <= 0) return left == 0;
+  if (strict) return false;
+  if (left == 16384 && c.limit[1] == 1u) return true;  // half the space used by one 1-bit code
+  return may_be_empty && left == 32768;
 }
 
 __device__ __forceinline__ uint32_t len_base(uint32_t s) { return kLenBase[s]; }  // s = symbol - 257, 0..28
@@ -383,6 +396,11 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8_inflate(const InflateDes
       if (type == 0u) {  // stored: the whole bytes left in the bit buffer, then the rest straight from the input
         br.buf >>= (br.n & 7u);
         br.n -= br.n & 7u;
+        // Bits above the count may be left in the buffer: the look-ahead of the
+        // byte at p (see fill).  The stored bytes move p on without a fill, and
+        // the next fill would OR another byte onto them.  From a whole number of
+        // bytes on, a fill leaves none.
+        br.buf = br.n ? br.buf & (~0ull >> (64u - br.n)) : 0ull;
         const uint32_t SL = br.get(16, W.in, base, len), NL = br.get(16, W.in, base, len);
         if ((SL ^ 0xFFFFu) != NL) {
           st = kErrStored;
@@ -415,7 +433,7 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8_inflate(const InflateDes
         if (st == kOk) {
           for (int s = 0; s < 19; s++) W.lens[s] = 0;
           for (uint32_t s = 0; s < ncode; s++) W.lens[kOrder[s]] = (uint8_t)br.get(3, W.in, base, len);
-          if (!construct(W.lc, W.lsym, W.next, W.lens, 19)) st = kErrCode;
+          if (!code_usable(construct(W.lc, W.lsym, W.next, W.lens, 19), W.lc, true, false)) st = kErrCode;
         }
         uint32_t idx = 0;
         while (st == kOk && idx < nlen + ndist) {
@@ -454,7 +472,8 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8_inflate(const InflateDes
         if (st == kOk) {
           for (uint32_t s = 0; s < 30u; s++) W.dlens[s] = s < ndist ? W.lens[nlen + s] : 0u;
           for (uint32_t s = nlen; s < 288u; s++) W.lens[s] = 0u;
-          if (!construct(W.lc, W.lsym, W.next, W.lens, 288) || !construct(W.dc, W.dsym, W.next, W.dlens, 30))
+          if (!code_usable(construct(W.lc, W.lsym, W.next, W.lens, 288), W.lc, false, false) ||
+              !code_usable(construct(W.dc, W.dsym, W.next, W.dlens, 30), W.dc, false, true))
             st = kErrCode;
         }
       }
@@ -760,7 +779,7 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8_inflate_lanes(const Infl
       }
       for (int s = 0; s < 19; s++) T.lens[s] = 0;
       for (uint32_t s = 0; s < ncode; s++) T.lens[kOrder[s]] = (uint8_t)br.get(3);
-      if (!construct(T.lc, T.lsym, T.next, T.lens, 19)) {
+      if (!code_usable(construct(T.lc, T.lsym, T.next, T.lens, 19), T.lc, true, false)) {
         st = kErrCode;
         break;
       }
@@ -802,11 +821,11 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8_inflate_lanes(const Infl
       // distance lengths first (they sit after the literal/length ones in lens)
       for (uint32_t s = 0; s < 30u; s++) T.dlens[s] = s < ndist ? T.lens[nlen + s] : 0u;
       for (uint32_t s = nlen; s < 288u; s++) T.lens[s] = 0u;
-      if (!construct(T.lc, T.lsym, T.next, T.lens, 288)) {
+      if (!code_usable(construct(T.lc, T.lsym, T.next, T.lens, 288), T.lc, false, false)) {
         st = kErrCode;
         break;
       }
-      if (!construct(T.dc, T.dsym, T.next, T.dlens, 30)) {
+      if (!code_usable(construct(T.dc, T.dsym, T.next, T.dlens, 30), T.dc, false, true)) {
         st = kErrCode;
         break;
       }

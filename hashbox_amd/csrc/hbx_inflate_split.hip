@@ -400,6 +400,7 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8s_decode(const InflateDes
       if (type == 0u) {
         br.buf >>= (br.n & 7u);
         br.n -= br.n & 7u;
+        br.buf = br.n ? br.buf & (~0ull >> (64u - br.n)) : 0ull;  // (the look-ahead bits: see hbx_k8_inflate)
         const uint32_t SL = br.get(16, W.in, base, len), NL = br.get(16, W.in, base, len);
         if ((SL ^ 0xFFFFu) != NL) st = kStBad;
         else {
@@ -427,7 +428,7 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8s_decode(const InflateDes
         if (st == 0u) {
           for (int s = 0; s < 19; s++) W.lens[s] = 0;
           for (uint32_t s = 0; s < ncode; s++) W.lens[kOrder[s]] = (uint8_t)br.get(3, W.in, base, len);
-          if (!construct(W.lc, W.lsym, W.next, W.lens, 19)) st = kStBad;
+          if (!code_usable(construct(W.lc, W.lsym, W.next, W.lens, 19), W.lc, true, false)) st = kStBad;
         }
         uint32_t idx = 0;
         while (st == 0u && idx < nlen + ndist) {
@@ -466,7 +467,8 @@ extern "C" __global__ __launch_bounds__(64) void hbx_k8s_decode(const InflateDes
         if (st == 0u) {
           for (uint32_t s = 0; s < 30u; s++) W.dlens[s] = s < ndist ? W.lens[nlen + s] : 0u;
           for (uint32_t s = nlen; s < 288u; s++) W.lens[s] = 0u;
-          if (!construct(W.lc, W.lsym, W.next, W.lens, 288) || !construct(W.dc, W.dsym, W.next, W.dlens, 30))
+          if (!code_usable(construct(W.lc, W.lsym, W.next, W.lens, 288), W.lc, false, false) ||
+              !code_usable(construct(W.dc, W.dsym, W.next, W.dlens, 30), W.dc, false, true))
             st = kStBad;
         }
       }
@@ -614,6 +616,21 @@ extern "C" __global__ __launch_bounds__(256) void hbx_k8s_resolve(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     bool bad = false;
+    // A marker that reaches before the start of the output (a corrupt stream;
+    // only possible while pos < 32768, and region 0 has no markers) is found
+    // before any byte of this region is written: the sequential kernel stops
+    // at that token, and the bytes written here must not run past the length
+    // it then reports.
+    if (cur != 0u && pos < 32768u) {
+      for (uint32_t q = tid; q < n; q += 256u) {
+        const uint32_t v = sy[q];
+        if ((v & 0x8000u) && pos + (v & 0x7FFFu) < 32768u) bad = true;
+      }
+      if (__syncthreads_or(bad)) {
+        ok = false;
+        break;
+      }
+    }
     for (uint32_t q = tid; q < n; q += 256u) {
       const uint32_t v = sy[q];
       uint32_t x;

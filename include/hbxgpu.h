@@ -493,8 +493,15 @@ int hbx_verify_submit_device(hbx_ctx *ctx, const void *d_arena, uint64_t n, cons
  * out_caps[i] bytes); out_lens[i] (host) = inflated bytes, status[i] (host) =
  * 0, or 1 bad header / Adler-32, 2 truncated input, 3 output capacity,
  * 4 invalid code, 5 distance too far back, 6 bad stored length.  Any RFC
- * 1950 stream (Go's compress/zlib, K7's).  A corrupt stream only sets its
- * status.  Then hbx_verify_blocks_device / hbx_verify_submit_device on the
+ * 1950 stream (Go's compress/zlib, K7's).  Status 4 covers what zlib and
+ * Go's flate refuse in a block's codes: block type 3, more than 286
+ * literal/length or 30 distance lengths, a repeat with nothing to repeat or
+ * past the last length, no code for end-of-block, an over-subscribed code,
+ * a symbol without a code, and an incomplete code: the code-length code must
+ * be complete, a literal/length or distance code too unless it is a single
+ * code of length 1, or a distance code of no codes at all (literals only).
+ * A corrupt stream only sets its status; out_lens[i] is then what was
+ * written before it was found, and no byte past it changes.  Then hbx_verify_blocks_device / hbx_verify_submit_device on the
  * output is VerifyBlock of compressed blocks (block.go:152-166).  This call
  * needs each stream's inflated size in advance; a block read back from a
  * server carries its compressed length only (Unserialize, block.go:82-94):

@@ -38,8 +38,12 @@ def _datas():
     rng = np.random.default_rng(3)
     out = []
     for n in (0, 1, 100, 32768, 40000, 300_000):
-        out += [rng.integers(0, 256, n, dtype=np.uint8).tobytes(), _text(n, n), bytes(n),
-                (rng.integers(0, 256, 33000, dtype=np.uint8).tobytes() * (n // 33000 + 1))[:n]]  # far matches
+        out += [rng.integers(0, 256, n, dtype=np.uint8).tobytes(), _text(n, n), bytes(n)]
+        # random bytes repeated with a period: 33,000 is beyond the window, so zlib
+        # finds no match at all (stored blocks only); 30,000 and 32,506 (zlib's
+        # longest distance, window - 262) it does match, at exactly that distance
+        for period in (33000, 30000, 32506):
+            out.append((rng.integers(0, 256, period, dtype=np.uint8).tobytes() * (n // period + 1))[:n])
     return out
 
 

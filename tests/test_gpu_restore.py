@@ -280,6 +280,27 @@ def test_oversized_stream_and_unknown_type(engine):
     assert r.status.tolist() == [0] and r.data == blocks[1]
 
 
+def test_crafted_streams_restore_and_verify(engine, oracle):
+    """Hand-built streams (tests/deflate_craft.py) through the whole restore:
+    a match at the full window distance, stored blocks whose payload is itself
+    zlib streams, and a 1000:1 chain of overlapping copies, which outgrows the
+    size the restore path guesses from the compressed length.  The IDs are the
+    oracle's.  Then a chain whose second block carries an incomplete Huffman
+    code, which zlib refuses: the prefix rule stops there."""
+    from tests import deflate_craft as C
+    by = {c.name: c for c in C.far() + C.split_may_fall_back() + C.chains() + C.rejections()}
+    cases = [by["far_D32768_L258"], by["stored_payload_of_zlib_streams"], by["chain_dynamic_1000_to_1"]]
+    ids = [oracle.block_id(np.frombuffer(c.expected, np.uint8)) for c in cases]
+    assert ids == [block_id(c.expected) for c in cases]
+    r = engine.restore_blocks([c.stream for c in cases], [ZLIB] * 3, ids)
+    assert r.status.tolist() == [0, 0, 0] and r.n_good == 3
+    assert r.data == b"".join(c.expected for c in cases)
+    bad = by["incomplete_litlen_code"]
+    r = engine.restore_blocks([cases[0].stream, bad.stream, cases[2].stream], [ZLIB] * 3, [ids[0], bytes(16), ids[2]])
+    assert r.n_good == 1 and int(r.status[1]) != 0 and int(r.status[0]) == 0
+    assert r.data == cases[0].expected
+
+
 def test_out_cap_smaller_than_the_prefix_is_an_argument_error(engine):
     from hashbox_amd import HbxError
     blocks, ids, zs = chain8()
