@@ -42,6 +42,7 @@ EXPORTS = [
     "hbx_seg_submit_device_dd", "hbx_store_file_stream",
     "hbx_restore_in_bound", "hbx_restore_blocks", "hbx_restore_file_stream",
     "hbx_restore_many_window", "hbx_restore_files_blocks", "hbx_restore_files_stream",
+    "hbx_match_chains", "hbx_submit_device_match", "hbx_store_paths_match",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -120,6 +121,12 @@ class RestoredFile(ctypes.Structure):
     """hbx_restored_file: one file's result of hbx_restore_files_stream."""
     _fields_ = [("bytes", ctypes.c_uint64), ("n_good", ctypes.c_uint64), ("bad_index", ctypes.c_uint64),
                 ("first_diff", ctypes.c_uint64), ("bad_status", ctypes.c_uint32), ("err", ctypes.c_int32)]
+
+
+class ChainMatch(ctypes.Structure):
+    """hbx_chain_match: one file's local ID list against its stored chain (K12)."""
+    _fields_ = [("n_match", ctypes.c_uint32), ("n_local", ctypes.c_uint32), ("n_expect", ctypes.c_uint32),
+                ("same", ctypes.c_uint32), ("match_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
 BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
@@ -256,6 +263,9 @@ def load() -> ctypes.CDLL:
     L.hbx_restore_many_window.argtypes = [U64, P, U64, U64, PU64]
     L.hbx_restore_files_blocks.argtypes = [P, U64, P, P, P, P, P, P, P, P, P, U64, P, U64, P, P, P, P, P, P, P]
     L.hbx_restore_files_stream.argtypes = [P, U64, P, P, P, P, P, U64, P, P, ctypes.c_uint32, U64, P]
+    L.hbx_match_chains.argtypes = [P, U64, P, P, P, P, P, P]
+    L.hbx_submit_device_match.argtypes = L.hbx_submit_device.argtypes + [P, P, P]
+    L.hbx_store_paths_match.argtypes = [P, U64, P, P, P, P, P, P, P, P, ctypes.c_uint32, U64, P, P, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

@@ -41,6 +41,7 @@
 #include "hbx_inflate.hip"
 #include "hbx_inflate_split.hip"
 #include "hbx_dedup.hip"
+#include "hbx_match.hip"
 #include "hbx_restore.hip"
 #include "hbx_restore_many.hip"
 #include "hbx_formats.h"
@@ -118,9 +119,10 @@ struct TimedLaunch {
 struct ResLayout {
   size_t counts = 0, cuts = 0, ids = 0, cid = 0, ctype = 0, total = 0;
   size_t fresh = 0;  // K9 flags, one byte per result slot: only for a batch submitted with an ID set
+  size_t match = 0;  // K12 records, 32 bytes per file: only for a batch submitted with expected chains
 };
 inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-ResLayout res_layout(uint64_t n_files, uint64_t total_cap, bool dedup = false) {
+ResLayout res_layout(uint64_t n_files, uint64_t total_cap, bool dedup = false, bool match = false) {
   ResLayout r;
   r.cuts = al256(n_files * 4);
   r.ids = r.cuts + al256(total_cap * 8);
@@ -130,6 +132,11 @@ ResLayout res_layout(uint64_t n_files, uint64_t total_cap, bool dedup = false) {
   if (dedup) {  // behind everything else: the layout and the copy of a batch without a set do not change
     r.fresh = r.total;
     r.total += al256(total_cap);
+  }
+  if (match) {  // likewise behind everything else; without a set it follows the content ids and types, so a
+                // verdict-only batch pushes [cid, total): its per-file sections in one contiguous range
+    r.match = r.total;
+    r.total += al256(n_files * sizeof(hbx_chain_match));
   }
   return r;
 }
@@ -214,12 +221,22 @@ struct Batch {
   hbx_idset* set = nullptr;
   uint8_t* fresh_out = nullptr;
   uint64_t dd_seq = 0;
+  // submitted with expected chains (hbx_submit_device_match, hbx_store_paths_match): K12 compares each
+  // file's result slots with its expected chain when the batch is finalized.  h_exp is the copy made at
+  // submit (n + 1 running counts | the IDs), fetched into d_exp for K12; the records go to match_out[f] at the
+  // collect.  verdict_only: the caller gave no chunk arrays, and only [rl.cid, rl.total) is pushed
+  PinBuf h_exp;
+  DevBuf d_exp;
+  size_t exp_ids_at = 0, exp_bytes = 0;  // (exp_bytes: a multiple of 16)
+  hbx_chain_match* match_out = nullptr;
+  bool verdict_only = false;
   // K1 start | K1 end | K2r end | plan+K3 end (first) | results ready | K2 end (lean marks)
   hipEvent_t ev[6] = {};
   void release() {
-    for (DevBuf* d : {&d_meta, &d_res, &d_run, &d_fresh, &d_fcnt}) d->release();
+    for (DevBuf* d : {&d_meta, &d_res, &d_run, &d_fresh, &d_fcnt, &d_exp}) d->release();
     h_meta.release();
     h_res.release();
+    h_exp.release();
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -425,6 +442,8 @@ struct hbx_ctx {
   std::vector<hbx_idset*> idsets;
   DevBuf d_dscratch;
   uint64_t dd_submitted = 0, dd_marked = 0;
+  uint64_t match_push_bytes = 0;  // hbx_knobs: bytes of the result pushes of match batches
+  DevBuf d_mt[5], d_mtout;        // hbx_match_chains: the two ID lists, their firsts, the cut ends; the records
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -595,6 +614,8 @@ Batch* acquire_batch(hbx_ctx* c) {
   b->set = nullptr;
   b->fresh_out = nullptr;
   b->dd_seq = 0;
+  b->match_out = nullptr;
+  b->verdict_only = false;
   return b;
 }
 
@@ -683,15 +704,38 @@ int finalize_batch(hbx_ctx* c, Batch* b) {
                          (uint32_t)n};
       HBX_TRY(c, hbxd::mark(s, b->set->view(), in, c->d_dscratch.as<uint32_t>(), b->res(b->rl.fresh)));
     }
+    // what the push brings back: everything, or a verdict-only batch's per-file sections
+    size_t push_at = 0;
+    if (b->match_out) {
+      // K12: every chain of the batch is hashed here, whatever the slice, join lag and K3 period.  The
+      // expected chains come over PCIe from the batch's pinned copy by hbx_meta_fetch (system-scope reads:
+      // the staging is reused by later batches), a kernel and not an SDMA copy between two kernels of this
+      // stream
+      const uint32_t e16 = (uint32_t)(b->exp_bytes / 16);
+      hipLaunchKernelGGL(hbx_meta_fetch, dim3(std::min<uint32_t>(64, (e16 + 255) / 256)), dim3(256), 0, s,
+                         static_cast<const uint4*>(b->h_exp.p), b->d_exp.as<uint4>(), e16);
+      HBX_TRY(c, hipGetLastError());
+      const uint8_t* he = b->d_exp.as<uint8_t>();
+      const hbxm::Args ma{hbxd::Ids{reinterpret_cast<const uint4*>(b->res(b->rl.ids)), d_cb, b->count_d(),
+                                    (uint32_t)b->caps, (uint32_t)n},
+                          b->cuts_d(), reinterpret_cast<const uint64_t*>(he),
+                          reinterpret_cast<const uint4*>(he + b->exp_ids_at),
+                          reinterpret_cast<uint4*>(b->res(b->rl.match))};
+      HBX_TRY(c, hbxm::match(s, ma));
+      if (b->verdict_only) push_at = b->rl.cid;
+      c->match_push_bytes += b->rl.total - push_at;
+    }
     g_slow.lap(0, lap);
     // one copy for every result (5 copies before: each a dispatch on this stream)
     if (c->d2h_kernel && b->rl.total % 16 == 0) {
-      const uint64_t n16 = b->rl.total / 16;
+      const uint64_t n16 = (b->rl.total - push_at) / 16;
       hipLaunchKernelGGL(hbx_result_push, dim3((uint32_t)std::min<uint64_t>(c->d2h_kernel, (n16 + 255) / 256)),
-                         dim3(256), 0, s, b->d_res.as<uint4>(), static_cast<uint4*>(b->h_res.p), n16);
+                         dim3(256), 0, s, reinterpret_cast<const uint4*>(b->res(push_at)),
+                         reinterpret_cast<uint4*>(b->h_res.as<uint8_t>() + push_at), n16);
       HBX_TRY(c, hipGetLastError());
     } else {
-      HBX_TRY(c, hipMemcpyAsync(b->h_res.p, b->d_res.p, b->rl.total, hipMemcpyDeviceToHost, s));
+      HBX_TRY(c, hipMemcpyAsync(b->h_res.as<uint8_t>() + push_at, b->res(push_at), b->rl.total - push_at,
+                                hipMemcpyDeviceToHost, s));
     }
     g_slow.lap(1, lap);
   }
@@ -1095,30 +1139,41 @@ inline uint64_t scan_iters(uint64_t N) {  // K1 iterations of a file (0: no spli
 // collected by wait_oldest in submission order.  Every validation and
 // allocation happens before the batch joins the FIFO; a failure after that
 // removes it again (submit_abort), so a failed submit leaves no pending batch.
+// The expected chains of a match batch (hbx_submit_device_match, hbx_store_paths_match): file f's chain is
+// ids[16 first[f] .. 16 first[f + 1]) (validated by the caller: non-decreasing, each chain below 2^32
+// IDs); out[f] receives its record at the collect.  verdict_only: no chunk arrays, out_base and caps NULL.
+struct MatchIn {
+  const uint64_t* first = nullptr;
+  const uint8_t* ids = nullptr;
+  hbx_chain_match* out = nullptr;
+  bool verdict_only = false;
+};
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                        const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
-                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh);
+                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh, const MatchIn* mi);
 }  // namespace
 // hbx_reserve with the context's lock already held (defined beside it, inside
 // the C-ABI block; not exported)
 extern "C" __attribute__((visibility("hidden"))) int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files,
-                                                                    uint64_t bytes, bool dedup = false);
+                                                                    uint64_t bytes, bool dedup = false,
+                                                                    bool match = false, uint64_t match_ids = 0);
 namespace {
 int submit_batch(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                  const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                  const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs = nullptr,
-                 const uint64_t* seg_offs = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr) {
+                 const uint64_t* seg_offs = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr,
+                 const MatchIn* mi = nullptr) {
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = submit_batch_timed(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, budget, segs,
-                                    seg_offs, set, fresh);
+                                    seg_offs, set, fresh, mi);
   c->max_submit_ms = std::max(c->max_submit_ms, ms_since(t0));
   return rc;
 }
 int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                        const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base,
                        const uint64_t* caps, hbx_file_summary* sums, uint32_t budget, hbx_seg* const* segs,
-                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh) {
+                       const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh, const MatchIn* mi) {
   g_slow.mark(0);
   g_slow.clear();
   if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
@@ -1131,8 +1186,14 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
   b->cut_ends = cut_ends;
   b->ids = ids;
   b->sums = sums;
-  b->out_base.assign(out_base, out_base + n);
-  b->capv.assign(caps, caps + n);
+  if (out_base) {
+    b->out_base.assign(out_base, out_base + n);
+    b->capv.assign(caps, caps + n);
+  } else {  // verdict-only: nothing is scattered; the result slots are sized by hbx_max_chunks(len)
+    b->out_base.assign(n, 0);
+    b->capv.resize(n);
+    for (uint64_t f = 0; f < n; f++) b->capv[f] = max_chunks(lens[f]);
+  }
   b->cut_base.resize(n);
   if (segs) {  // (validated by the caller: seg_submit)
     b->segs.assign(segs, segs + n);
@@ -1183,7 +1244,22 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
   g_slow.mark(1);
   if (n) {  // every allocation first: the batch is not in the FIFO yet
     int rc = HBX_OK;
-    b->rl = res_layout(n, tcaps, set != nullptr);
+    b->rl = res_layout(n, tcaps, set != nullptr, mi != nullptr);
+    if (mi) {  // firsts (rebased to 0) | IDs, copied now: the caller's arrays are free on return
+      const uint64_t e0 = mi->first[0], ne = mi->first[n] - e0;
+      b->exp_ids_at = al256((n + 1) * 8);
+      b->exp_bytes = b->exp_ids_at + 16 * ne;
+      for (hipError_t e : {b->h_exp.ensure(b->exp_bytes), b->d_exp.ensure(b->exp_bytes)})
+        if (e != hipSuccess && !rc) rc = c->hip(e, "batch buffers (expected chains)");
+      if (!rc) {
+        uint64_t* hf = b->h_exp.as<uint64_t>();
+        for (uint64_t f = 0; f <= n; f++) hf[f] = mi->first[f] - e0;
+        std::memset(hf + n + 1, 0, b->exp_ids_at - (n + 1) * 8);
+        if (ne) std::memcpy(b->h_exp.as<uint8_t>() + b->exp_ids_at, mi->ids + 16 * e0, 16 * ne);
+        b->match_out = mi->out;
+        b->verdict_only = mi->verdict_only;
+      }
+    }
     for (hipError_t e : {b->h_meta.ensure(meta_bytes), b->d_meta.ensure(meta_bytes), b->d_res.ensure(b->rl.total),
                          b->d_run.ensure(tcaps * sizeof(Chain)),
                          b->d_fresh.ensure(tcaps * sizeof(OrderEntry)), b->d_fcnt.ensure(256),
@@ -1563,9 +1639,12 @@ int collect_batch(hbx_ctx* c, Batch* b) {
   const uint8_t* cid = hr + rl.cid;
   const int32_t* ctype = reinterpret_cast<const int32_t*>(hr + rl.ctype);
   int rc = b->segs.empty() ? HBX_OK : collect_segments(c, b);
+  // (a verdict-only batch pushed [rl.cid, rl.total) only: the chunk count comes from the file's record)
+  const hbx_chain_match* mt = b->match_out ? reinterpret_cast<const hbx_chain_match*>(hr + rl.match) : nullptr;
   for (uint64_t f = 0; f < n && b->segs.empty(); f++) {
-    const uint64_t k = counts[f];
+    const uint64_t k = b->verdict_only ? mt[f].n_local : counts[f];
     const uint64_t ib = b->cut_base[f];
+    if (mt) b->match_out[f] = mt[f];
     if (b->sums) {
       std::memcpy(b->sums[f].content_id, cid + 16 * f, 16);
       b->sums[f].content_type = ctype[f];
@@ -1867,6 +1946,8 @@ void hbx_ctx_destroy(hbx_ctx* c) {
     delete t;
   }
   c->d_dscratch.release();
+  for (DevBuf& d : c->d_mt) d.release();
+  c->d_mtout.release();
   for (hbx_seg* h : c->segs_open) delete h;
   for (DevBuf& d : c->seg_words) d.release();
   c->d_segmsg.release();
@@ -2034,14 +2115,16 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"plan_cut\": %u, \"k1_swz\": %u, \"k3_psets\": %u, \"d2h_kernel\": %u, \"k8_split_streams\": %llu, "
       "\"k8_split_fallbacks\": %llu, \"gate_meta\": %u, \"sdma_warm\": %u, \"sdma_h2d_mask\": %u, "
       "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
-      "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu]}",
+      "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu], "
+      "\"match_push_bytes\": %llu}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
       (unsigned long long)c->k8_split_streams, (unsigned long long)c->k8_split_fallbacks, c->gate_meta,
       c->sdma_warm, c->sdma_h2d, c->sdma_d2h, c->sdma_warm_ms, c->k3_spin, c->plan_addr, c->plan_addr_shift, c->k1_ext, c->k1_dma4, c->k1_early,
       c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3],
-      (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries);
+      (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries,
+      (unsigned long long)c->match_push_bytes);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -2099,7 +2182,8 @@ int hbx_reserve(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes) {
   return reserve_locked(c, batches, files, bytes);
 }
 
-int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes, bool dedup) {
+int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes, bool dedup, bool match,
+                   uint64_t match_ids) {
   if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
   HBX_TRY(c, hipSetDevice(c->device));
   const uint64_t caps = bytes / HBX_MIN_BLOCK_SIZE + files;  // >= sum of max_chunks over the files
@@ -2121,7 +2205,12 @@ int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes,
     Batch* b = acquire_batch(c);  // pooled first, then new
     if (!b) break;
     ready.push_back(b);
-    const size_t rbytes = res_layout(files, caps, dedup).total;
+    const size_t rbytes = res_layout(files, caps, dedup, match).total;
+    if (match) {  // the staging of the batch's expected chains: the steady state allocates nothing
+      const size_t ebytes = al256((files + 1) * 8) + 16 * match_ids;
+      for (auto r : {b->h_exp.ensure(ebytes), b->d_exp.ensure(ebytes)})
+        if (r != hipSuccess && !rc) rc = c->hip(r, "hbx_reserve");
+    }
     for (auto r : {b->h_meta.ensure(meta_bytes), b->d_meta.ensure(meta_bytes), b->d_res.ensure(rbytes),
                    b->d_run.ensure(caps * sizeof(Chain)), b->d_fresh.ensure(caps * sizeof(OrderEntry)),
                    b->d_fcnt.ensure(256), b->h_res.ensure(rbytes)})
@@ -2180,6 +2269,80 @@ int hbx_submit_device_dd(hbx_ctx* c, const void* d_arena, uint64_t n, const uint
   HBX_TRY(c, hipSetDevice(c->device));
   return submit_batch(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums,
                       c->md5_slice ? c->md5_slice : kBudgetAll, nullptr, nullptr, set, set ? fresh : nullptr);
+}
+
+namespace {
+// The checks the match calls share, before the context is touched: *vo = verdict-only mode.
+int match_args(uint64_t n, uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
+               const uint64_t* first, const uint8_t* eids, const hbx_chain_match* out, bool* vo) {
+  if (!out) return HBX_ERR_ARG;
+  *vo = !out_base && !caps;
+  if (*vo ? (cut_ends || ids) : (n && (!out_base || !caps))) return HBX_ERR_ARG;
+  for (uint64_t f = 0; f < n; f++)
+    if (first[f + 1] < first[f] || first[f + 1] - first[f] > 0xFFFFFFFFull) return HBX_ERR_ARG;
+  if (first[n] > first[0] && !eids) return HBX_ERR_ARG;
+  return HBX_OK;
+}
+}  // namespace
+
+int hbx_submit_device_match(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs, const uint64_t* lens,
+                            uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
+                            hbx_file_summary* sums, const uint64_t* expect_first, const uint8_t* expect_ids,
+                            hbx_chain_match* match) {
+  if (!c) return HBX_ERR_ARG;
+  if (!expect_first) return hbx_submit_device(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums);
+  if (n && (!d_arena || !offs || !lens)) return HBX_ERR_ARG;
+  bool vo = false;
+  if (int rc = match_args(n, cut_ends, ids, out_base, caps, expect_first, expect_ids, match, &vo)) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  HBX_TRY(c, hipSetDevice(c->device));
+  const MatchIn mi{expect_first, expect_ids, match, vo};
+  return submit_batch(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums,
+                      c->md5_slice ? c->md5_slice : kBudgetAll, nullptr, nullptr, nullptr, nullptr, &mi);
+}
+
+int hbx_match_chains(hbx_ctx* c, uint64_t n, const uint64_t* local_first, const uint8_t* local_ids,
+                     const uint64_t* local_cut_ends, const uint64_t* expect_first, const uint8_t* expect_ids,
+                     hbx_chain_match* match) {
+  if (!c) return HBX_ERR_ARG;
+  if (n == 0) return HBX_OK;
+  if (!local_first || !expect_first || !match || n > 0x7FFFFFFFull) return HBX_ERR_ARG;
+  for (uint64_t f = 0; f < n; f++)
+    if (local_first[f + 1] < local_first[f] || expect_first[f + 1] < expect_first[f] ||
+        expect_first[f + 1] - expect_first[f] > 0xFFFFFFFFull)
+      return HBX_ERR_ARG;
+  const uint64_t l0 = local_first[0], nl = local_first[n] - l0, e0 = expect_first[0], ne = expect_first[n] - e0;
+  if (nl > 0xFFFFFFFFull || (nl && !local_ids) || (ne && !expect_ids)) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  HBX_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->rstream;
+  // K12 alone, as hbx_idset_insert runs K9 alone: the lists staged in device memory, firsts rebased to 0
+  std::vector<uint64_t> fl(n + 1), fe(n + 1);
+  for (uint64_t f = 0; f <= n; f++) {
+    fl[f] = local_first[f] - l0;
+    fe[f] = expect_first[f] - e0;
+  }
+  const bool cuts = local_cut_ends && nl;
+  HBX_TRY(c, c->d_mt[0].ensure((n + 1) * 8));
+  HBX_TRY(c, c->d_mt[1].ensure((n + 1) * 8));
+  HBX_TRY(c, c->d_mt[2].ensure(nl * 16));
+  HBX_TRY(c, c->d_mt[3].ensure(ne * 16));
+  if (cuts) HBX_TRY(c, c->d_mt[4].ensure(nl * 8));
+  HBX_TRY(c, c->d_mtout.ensure(n * sizeof(hbx_chain_match)));
+  HBX_TRY(c, hipMemcpyAsync(c->d_mt[0].p, fl.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  HBX_TRY(c, hipMemcpyAsync(c->d_mt[1].p, fe.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+  if (nl) HBX_TRY(c, hipMemcpyAsync(c->d_mt[2].p, local_ids + 16 * l0, nl * 16, hipMemcpyHostToDevice, s));
+  if (ne) HBX_TRY(c, hipMemcpyAsync(c->d_mt[3].p, expect_ids + 16 * e0, ne * 16, hipMemcpyHostToDevice, s));
+  if (cuts) HBX_TRY(c, hipMemcpyAsync(c->d_mt[4].p, local_cut_ends + l0, nl * 8, hipMemcpyHostToDevice, s));
+  const hbxm::Args ma{hbxd::Ids{c->d_mt[2].as<uint4>(), c->d_mt[0].as<uint64_t>(), nullptr, (uint32_t)nl, (uint32_t)n},
+                      cuts ? c->d_mt[4].as<uint64_t>() : nullptr, c->d_mt[1].as<uint64_t>(), c->d_mt[3].as<uint4>(),
+                      c->d_mtout.as<uint4>()};
+  HBX_TRY(c, hbxm::match(s, ma));
+  HBX_TRY(c, hipMemcpyAsync(match, c->d_mtout.p, n * sizeof(hbx_chain_match), hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipStreamSynchronize(s));
+  return HBX_OK;
 }
 
 int hbx_wait(hbx_ctx* c) {
@@ -2889,7 +3052,8 @@ int z_finish(const hbx_ctx* c, ZPend& zp, const uint64_t* out_base, const hbx_fi
 int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
                      uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
                      hbx_file_summary* sums, uint32_t io_threads, uint64_t batch_bytes, const ZOut& z,
-                     int32_t* status = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr);
+                     int32_t* status = nullptr, hbx_idset* set = nullptr, uint8_t* fresh = nullptr,
+                     const MatchIn* mi = nullptr);
 }  // namespace
 
 int hbx_store_paths(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
@@ -2931,6 +3095,24 @@ int hbx_store_paths_dd(hbx_ctx* c, uint64_t n, const char* const* paths, const u
   return store_paths_impl(c, n, paths, lens, cut_ends, ids, out_base, caps, sums, io_threads, batch_bytes,
                           z ? ZOut{zout, zbase, zoff, zlen, ready, user, set ? fresh : nullptr} : ZOut{}, status,
                           set, set ? fresh : nullptr);
+}
+
+int hbx_store_paths_match(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens, uint64_t* cut_ends,
+                          uint8_t* ids, const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums,
+                          int32_t* status, uint32_t io_threads, uint64_t batch_bytes, const uint64_t* expect_first,
+                          const uint8_t* expect_ids, hbx_chain_match* match) {
+  if (!c) return HBX_ERR_ARG;
+  if (!expect_first)
+    return hbx_store_paths_dd(c, n, paths, lens, cut_ends, ids, out_base, caps, sums, status, io_threads, batch_bytes,
+                              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  if (n && (!paths || !lens)) return HBX_ERR_ARG;
+  bool vo = false;
+  if (int rc = match_args(n, cut_ends, ids, out_base, caps, expect_first, expect_ids, match, &vo)) return rc;
+  std::lock_guard<std::mutex> g(c->mu);
+  for (uint64_t i = 0; status && i < n; i++) status[i] = 0;
+  const MatchIn mi{expect_first, expect_ids, match, vo};
+  return store_paths_impl(c, n, paths, lens, cut_ends, ids, out_base, caps, sums, io_threads, batch_bytes, ZOut{},
+                          status, nullptr, nullptr, &mi);
 }
 
 uint64_t hbx_deflate_file_bound(uint64_t len) {
@@ -2976,13 +3158,14 @@ size_t ring_depth(const hbx_ctx* c, uint32_t budget) {
 int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uint64_t* lens,
                      uint64_t* cut_ends, uint8_t* ids, const uint64_t* out_base, const uint64_t* caps,
                      hbx_file_summary* sums, uint32_t io_threads, uint64_t batch_bytes, const ZOut& z,
-                     int32_t* status, hbx_idset* set, uint8_t* fresh) {
+                     int32_t* status, hbx_idset* set, uint8_t* fresh, const MatchIn* mi) {
   if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
   HBX_TRY(c, hipSetDevice(c->device));
   // with an ID set the batch size is the caller's down to 1 MiB (the flags do
   // not depend on how the files fall into batches, and tests check that with
   // small files); without one it is at least 64 MiB, as ever
-  const uint64_t batch_min = set ? 1ull << 20 : 64ull << 20;
+  // (likewise with expected chains: the records do not depend on the batches either)
+  const uint64_t batch_min = set || mi ? 1ull << 20 : 64ull << 20;
   if (batch_bytes < batch_min) batch_bytes = batch_min;
   uint64_t set_count0 = 0;  // a failed call puts the set back to this
   if (set)
@@ -2999,9 +3182,10 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
   if (c->d_ring.size() < depth) c->d_ring.resize(depth);
   // size every staging buffer once, for the largest batch this call forms
   // (growing one later would re-pin host memory or drain the streams)
-  uint64_t biggest = 0, zbytes = 0, zchunks = 0, zsegs = 0, most_files = 0;
+  uint64_t biggest = 0, zbytes = 0, zchunks = 0, zsegs = 0, most_files = 0, most_expect = 0;
   for (uint64_t i = 0; i < n;) {
     uint64_t tot = 0, cnt = 0;
+    const uint64_t i0 = i;
     while (i < n && (cnt == 0 || tot + lens[i] <= batch_bytes) && cnt < 65536) {
       tot += (lens[i] + 255) & ~uint64_t(255);
       i++;
@@ -3009,6 +3193,7 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
     }
     biggest = std::max(biggest, tot);
     most_files = std::max(most_files, cnt);
+    if (mi) most_expect = std::max(most_expect, mi->first[i] - mi->first[i0]);
     // compression stage bounds of this batch: chunks <= a file's
     // max_chunks, a chunk's stream <= hbx_deflate_bound rounded to 16 B
     const uint64_t nch = tot / HBX_MIN_BLOCK_SIZE + cnt;
@@ -3037,7 +3222,8 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
   // pooled batch that met a larger batch later reallocated its pinned meta and
   // result buffers inside that submit (19-28 ms per submit of config 5,
   // HBX_TRACE_SLOW_SUBMIT "buffers", profiles/r06e)
-  if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, most_files, biggest, set != nullptr)) return r0;
+  if (int r0 = reserve_locked(c, (uint32_t)depth + 2u, most_files, biggest, set != nullptr, mi != nullptr, most_expect))
+    return r0;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   bool slot_used[2] = {false, false};
   std::vector<uint64_t> offs, skip_lens;
@@ -3150,9 +3336,11 @@ int store_paths_impl(hbx_ctx* c, uint64_t n, const char* const* paths, const uin
         if (status[i]) skip_lens[i - first] = 0;
       blens = skip_lens.data();
     }
+    MatchIn bm;  // this batch's share of the expected chains
+    if (mi) bm = MatchIn{mi->first + first, mi->ids, mi->out + first, mi->verdict_only};
     rc = submit_batch(c, arena.p, f - first, offs.data(), blens, cut_ends, ids,
-                      out_base + first, caps + first, sums ? sums + first : nullptr, budget, nullptr, nullptr, set,
-                      fresh);
+                      out_base ? out_base + first : nullptr, caps ? caps + first : nullptr,
+                      sums ? sums + first : nullptr, budget, nullptr, nullptr, set, fresh, mi ? &bm : nullptr);
     if (z.zout && rc == HBX_OK) jobs.push_back(ZJob{first, f - first, static_cast<const uint8_t*>(arena.p), offs});
     k++;
   }

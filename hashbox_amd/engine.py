@@ -116,6 +116,24 @@ class FileChunks:
 
 
 @dataclass(slots=True)
+class ChainMatch:
+    """One file's local block-ID list against its stored chain (hbx_chain_match,
+    K12).  ``same`` means the local file equals the stored one: a block ID binds
+    the block's length and bytes (block.go:96-111).  Not ``same`` means only
+    that the IDs do not settle it (a chain cut by another chunker names equal
+    bytes with other IDs): compare the bytes."""
+    same: bool  # n_match == n_local == n_expect
+    n_match: int  # length of the common prefix of the two ID lists
+    n_local: int  # chunks the local file was cut into (0 for a file skipped as unreadable)
+    n_expect: int  # IDs in the stored chain
+    match_bytes: int  # local offset where chunk n_match starts (the file's length when n_match == n_local)
+    errno: int = 0  # match_paths(skip_unreadable=True): the errno of a file skipped, else 0
+    content_type: int = 0  # of the LOCAL file, as FileChunks (0 from match_chains)
+    content_id: bytes = b""
+    chunks: Optional[FileChunks] = None  # the local file's chunks, where they were asked for
+
+
+@dataclass(slots=True)
 class SegmentChunks:
     """What ``Engine.store_file(..., on_segment=...)`` hands over per segment."""
     first_chunk: int  # index in the file of this segment's first chunk
@@ -191,6 +209,27 @@ def _ids_array(ids) -> np.ndarray:
     if a.size % 16:
         raise ValueError("block IDs are 16 bytes each")
     return a.reshape(-1, 16)
+
+
+def _chain_lists(chains) -> tuple:
+    """Per-file ID lists as (first uint64 [n + 1] running counts, ids uint8 [total, 16])."""
+    arrs = [_ids_array(c) if not (isinstance(c, (list, tuple)) and not c) else np.zeros((0, 16), np.uint8)
+            for c in chains]
+    first = np.zeros(len(arrs) + 1, np.uint64)
+    if arrs:
+        first[1:] = np.cumsum([a.shape[0] for a in arrs])
+    ids = np.ascontiguousarray(np.concatenate(arrs)) if arrs and int(first[-1]) else np.zeros((0, 16), np.uint8)
+    return first, ids
+
+
+def _matches(rec, n: int) -> list:
+    """hbx_chain_match records as ChainMatch objects."""
+    if n == 0:
+        return []
+    v = np.ctypeslib.as_array(rec)[:n]
+    return [ChainMatch(bool(s), int(m), int(l), int(e), int(b))
+            for s, m, l, e, b in zip(v["same"].tolist(), v["n_match"].tolist(), v["n_local"].tolist(),
+                                     v["n_expect"].tolist(), v["match_bytes"].tolist())]
 
 
 class IdSet:
@@ -437,10 +476,121 @@ class Engine:
                                               _p(caps), sums), "hbx_submit_device")
         self._pending.append((offs, lens, caps, base, cuts, ids, sums))
 
+    def submit_device_match(self, d_arena: int, offs: Sequence[int], lens: Sequence[int], chains_ids,
+                            chunks: bool = True):
+        """:meth:`submit_device` with each file's stored chain (a list of block
+        IDs per file; hbx_submit_device_match): K12 compares them on the
+        device once the batch is hashed, and :meth:`wait` returns one
+        :class:`ChainMatch` per file, with the file's FileChunks in
+        ``chunks``.  With ``chunks=False`` (verdict-only) the batch brings
+        back 52 bytes per file instead of 24 per result slot and ``chunks`` is
+        None.  The chains are copied by this call."""
+        self._after_producer()
+        offs = np.ascontiguousarray(offs, np.uint64)
+        lens = np.ascontiguousarray(lens, np.uint64)
+        if len(chains_ids) != len(lens):
+            raise ValueError("one chain per file")
+        first, eids = _chain_lists(chains_ids)
+        rec = (_lib.ChainMatch * max(len(lens), 1))()
+        if chunks:
+            out = self._alloc_out(lens)
+            caps, base, cuts, ids, sums = out
+            outp = (_p(cuts), _p(ids), base.ctypes.data, caps.ctypes.data)
+        else:
+            out, sums, outp = None, (_lib.FileSummary * max(len(lens), 1))(), (None, None, None, None)
+        self._check(self._L.hbx_submit_device_match(self._ctx, ctypes.c_void_p(int(d_arena)), len(lens), _p(offs),
+                                                    _p(lens), *outp, sums, first.ctypes.data, _p(eids), rec),
+                    "hbx_submit_device_match")
+        self._pending.append(("match", lens, out, sums, rec, offs))
+
+    def _match_result(self, lens, out, sums, rec, status=None) -> List[ChainMatch]:
+        n = len(lens)
+        res = _matches(rec, n)
+        if n == 0:
+            return res
+        sv = np.ctypeslib.as_array(sums)[:n]
+        cid = np.ascontiguousarray(sv["content_id"]).tobytes()
+        files = self._unpack(lens, *out) if out is not None else None
+        for f, (r, t) in enumerate(zip(res, sv["content_type"].tolist())):
+            r.content_type = int(t)
+            r.content_id = cid[16 * f:16 * f + 16] if r.n_local else b""
+            if files is not None:
+                r.chunks = files[f]
+            if status is not None:
+                r.errno = int(status[f])
+                if r.chunks is not None:
+                    r.chunks.errno = r.errno
+        return res
+
+    def match_chains(self, local_ids, expect_ids, local_cut_ends=None) -> List[ChainMatch]:
+        """K12 alone on ID lists the caller holds (hbx_match_chains): per file,
+        the common prefix of ``local_ids[f]`` and ``expect_ids[f]`` (lists of
+        16-byte IDs, or uint8 [k, 16] arrays).  ``local_cut_ends[f]`` (one per
+        local ID) gives ``match_bytes``; without them it is 0."""
+        if len(local_ids) != len(expect_ids):
+            raise ValueError("one expected chain per local ID list")
+        n = len(local_ids)
+        lf, lids = _chain_lists(local_ids)
+        ef, eids = _chain_lists(expect_ids)
+        cuts = None
+        if local_cut_ends is not None:
+            if len(local_cut_ends) != n:
+                raise ValueError("one list of cut ends per file")
+            cuts = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint64).reshape(-1) for c in local_cut_ends])
+                                        if n else np.zeros(0, np.uint64), np.uint64)
+            if cuts.shape[0] != lids.shape[0]:
+                raise ValueError("one cut end per local ID")
+        rec = (_lib.ChainMatch * max(n, 1))()
+        self._check(self._L.hbx_match_chains(self._ctx, n, lf.ctypes.data, _p(lids),
+                                             _p(cuts) if cuts is not None else None, ef.ctypes.data, _p(eids), rec),
+                    "hbx_match_chains")
+        return _matches(rec, n)
+
+    def match_paths(self, paths: Sequence[Union[str, os.PathLike]], chains_ids, io_threads: int = 16,
+                    batch_bytes: int = 1 << 30, sizes: Optional[Sequence[int]] = None,
+                    skip_unreadable: bool = False, chunks: bool = False) -> List[ChainMatch]:
+        """Cut and hash local files as :meth:`store_paths` does and compare each
+        file's block IDs with its stored chain ``chains_ids[f]`` on the device
+        (hbx_store_paths_match): what diffFileData learns by fetching and
+        comparing every block (restore.go:249-277), at the store path's speed
+        and without a data block off the wire.  A file that is ``same`` equals
+        the stored one; any other verdict leaves the question to the byte
+        comparison (:meth:`diff_files`).  ``chunks=False`` is the verdict-only
+        mode: 52 bytes per file come back.  ``chunks=True`` also returns each
+        file's FileChunks.  ``sizes``, ``skip_unreadable`` and ``batch_bytes``
+        (honoured down to 1 MiB) as in :meth:`store_paths`; the verdicts do not
+        depend on the batches."""
+        enc = [os.fsencode(p) for p in paths]
+        if len(chains_ids) != len(enc):
+            raise ValueError("one chain per path")
+        if sizes is None:
+            lens = np.array([os.stat(p).st_size for p in enc], np.uint64)
+        else:
+            lens = np.array(sizes, np.uint64).reshape(-1)
+            if lens.size != len(enc):
+                raise ValueError("sizes must have one entry per path")
+        arr = (ctypes.c_char_p * max(len(enc), 1))(*enc)
+        first, eids = _chain_lists(chains_ids)
+        rec = (_lib.ChainMatch * max(len(enc), 1))()
+        status = np.zeros(max(len(enc), 1), np.int32) if skip_unreadable else None
+        if chunks:
+            out = self._alloc_out(lens)
+            caps, base, cuts, ids, sums = out
+            outp = (_p(cuts), _p(ids), base.ctypes.data, caps.ctypes.data)
+        else:
+            out, sums, outp = None, (_lib.FileSummary * max(len(enc), 1))(), (None, None, None, None)
+        t0 = time.perf_counter()
+        self._check(self._L.hbx_store_paths_match(
+            self._ctx, len(enc), ctypes.cast(arr, ctypes.c_void_p), _p(lens), *outp, sums,
+            _p(status) if status is not None else None, int(io_threads), int(batch_bytes), first.ctypes.data,
+            _p(eids), rec), "hbx_store_paths_match")
+        self.last_call_s = time.perf_counter() - t0
+        return self._match_result(lens, out, sums, rec, status)
+
     def wait(self):
         """Results of the oldest submitted batch ([] if none is pending): a
         list of FileChunks for a chunking batch, (ids, ok, n_bad) for a
-        verify batch."""
+        verify batch, a list of ChainMatch for a match batch."""
         if not self._pending:
             return []
         item = self._pending.popleft()
@@ -459,6 +609,9 @@ class Engine:
                 for r, b in zip(res, base.astype(np.int64).tolist()):
                     r.fresh = fb[b:b + r.n_chunks]
             return res
+        if isinstance(item[0], str) and item[0] == "match":
+            _, lens, out, sums, rec, _keep = item
+            return self._match_result(lens, out, sums, rec)
         if isinstance(item[0], str):  # ("verify", ...)
             _, n, ids, ok, bad, keep = item
             return ids[:n], (ok[:n].astype(bool) if keep[1] is not None else None), int(bad.value)

@@ -359,11 +359,23 @@ def _file_chains(eng: Engine, read_block, entries: Sequence[FileEntry]) -> List[
     return ids
 
 
+def _create_file(local: bytes, e: FileEntry) -> int:
+    """Create or truncate ``local`` with the entry's mode, as OpenFile does
+    (restore.go:108: the umask applies); the mode the file has afterwards."""
+    fd = os.open(local, os.O_CREAT | os.O_TRUNC | os.O_WRONLY, e.file_mode & 0o777)
+    mode = stat.S_IMODE(os.fstat(fd).st_mode)
+    os.close(fd)
+    return mode
+
+
 def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: bytes, window_bytes: int,
-                          io_threads: int) -> Dict[str, int]:
+                          io_threads: int, keep_matching: bool = False) -> Dict[str, int]:
     stats = {"files": 0, "directories": 0, "bytes": 0}
+    if keep_matching:
+        stats["kept"] = 0
     made_dirs: List[Tuple[bytes, int]] = []
-    files: List[Tuple[FileEntry, bytes, int]] = []  # entry, local path, the mode its creation gave it
+    # entry, local path, the mode its creation gave it (None: a keep_matching candidate, not created yet)
+    files: List[Tuple[FileEntry, bytes, Optional[int]]] = []
     level: List[Tuple[FileEntry, bytes]] = [(root_entry, dest)]
     while level:  # breadth-first: one device call per level of directory blocks
         want: List[Tuple[FileEntry, bytes]] = []
@@ -384,14 +396,37 @@ def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: 
             else:  # restore.go:103-145
                 if e.content_type not in (TYPE_FILE_CHAIN, TYPE_FILE_DATA, TYPE_EMPTY):
                     raise HbxError(f"invalid ContentType for a file ({e.content_type})")
-                fd = os.open(local, os.O_CREAT | os.O_TRUNC | os.O_WRONLY, e.file_mode & 0o777)
-                mode = stat.S_IMODE(os.fstat(fd).st_mode)
-                os.close(fd)
-                files.append((e, local, mode))
+                # keep_matching: a regular file of the entry's size already there is neither created nor
+                # truncated until its block IDs have been compared with its chain
+                candidate = False
+                if keep_matching and int(e.file_size) > 0 and e.content_type != TYPE_EMPTY:
+                    try:
+                        st = os.lstat(local)
+                        candidate = stat.S_ISREG(st.st_mode) and st.st_size == int(e.file_size)
+                    except OSError:
+                        pass
+                files.append((e, local, None if candidate else _create_file(local, e)))
         blocks = _read_verified_many(eng, read_block, [e.content_block_id for e, _ in want], "directory")
         level = [(kid, local) for (_, local), blk in zip(want, blocks) for kid in parse_directory_block(blk)]
     ids = _file_chains(eng, read_block, [e for e, _, _ in files])
-    with_data = [k for k in range(len(files)) if ids[k]]
+    kept = set()
+    cand = [k for k in range(len(files)) if files[k][2] is None]
+    if cand:
+        # the local files cut and hashed at the store path's speed: one whose block IDs are its chain's is
+        # already right, and none of its data blocks is read
+        ms = eng.match_paths([files[k][1] for k in cand], [ids[k] for k in cand], io_threads=io_threads,
+                             sizes=[int(files[k][0].file_size) for k in cand], skip_unreadable=True)
+        umask = os.umask(0)
+        os.umask(umask)
+        for k, m in zip(cand, ms):
+            e, local, _ = files[k]
+            if m.same and not m.errno:
+                kept.add(k)
+                os.chmod(local, e.file_mode & 0o777 & ~umask)  # what creating it would have given it
+            else:
+                files[k] = (e, local, _create_file(local, e))
+        stats["kept"] = len(kept)
+    with_data = [k for k in range(len(files)) if ids[k] and k not in kept]
     # (a mode without the owner's write bit, 0444: writable while written, as in the unbatched path)
     locked = [k for k in with_data if not files[k][2] & stat.S_IWUSR]
     for k in locked:
@@ -421,7 +456,7 @@ def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: 
 
 
 def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_bytes: int = 0,
-                 batch: bool = False, io_threads: int = 16) -> Dict[str, int]:
+                 batch: bool = False, io_threads: int = 16, keep_matching: bool = False) -> Dict[str, int]:
     """restoreEntry(root_entry, dest) (hashback/restore.go:68-162): the
     counterpart of :func:`store_tree`.  ``read_block(id)`` returns a block as
     it comes off the wire: ``(data type, data field, links)``.
@@ -439,6 +474,16 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
     then data blocks in the order the files were met), and the good files of
     the same batch have been written by then (without their ModTime).
 
+    ``keep_matching=True`` (with ``batch=True``; a ValueError without it) is a
+    restore over an existing tree: a regular-file entry of FileSize > 0 whose
+    local path is already a regular file of that size is not created or
+    truncated during the walk; once the chains are read, those files are cut
+    and hashed by ``Engine.match_paths`` and one whose block IDs are its
+    chain's is kept as it is: only its permission bits and ModTime are set, no
+    data block of it is read, and it is counted in ``stats["kept"]``, not in
+    ``bytes``.  Every other candidate is created or truncated and restored
+    with the rest.
+
     Directory blocks and chain blocks are inflated and verified on the device
     with their links (``Engine.restore_blocks``), then parsed
     (``parse_directory_block`` / ``parse_chain_block``); regular files stream
@@ -449,9 +494,11 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
     content (restore.go:99).  Decrypt keys are ignored, as in the reference
     (restore.go:57).  Returns the counts ``{"files", "directories", "bytes"}``.
     """
+    if keep_matching and not batch:
+        raise ValueError("keep_matching needs batch=True")
     dest = os.fsencode(os.fspath(dest))
     if batch:
-        return _restore_tree_batched(eng, root_entry, read_block, dest, window_bytes, io_threads)
+        return _restore_tree_batched(eng, root_entry, read_block, dest, window_bytes, io_threads, keep_matching)
     stats = {"files": 0, "directories": 0, "bytes": 0}
 
     def restore_entry(e: FileEntry, path: bytes):
@@ -500,7 +547,7 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
 
 
 def diff_tree(eng: Engine, root_entry: FileEntry, read_block, local_root, window_bytes: int = 0,
-              io_threads: int = 16) -> Dict[str, object]:
+              io_threads: int = 16, by_id: bool = False) -> Dict[str, object]:
     """diffEntry(root_entry, local_root) with diffDir below it
     (hashback/restore.go:279-414): compare a stored tree with a local one.
 
@@ -513,6 +560,16 @@ def diff_tree(eng: Engine, root_entry: FileEntry, read_block, local_root, window
     in batched calls, as ``restore_tree(batch=True)`` does.  A name only one
     side has is reported for the whole of both listings (the reference's merge
     loop ends with the shorter one).  ``platformSafeFilename`` is not applied.
+
+    With ``by_id=True`` the files whose data would be compared are first cut
+    and hashed locally (``Engine.match_paths``) and their block IDs compared
+    with their chains: a block ID binds the block's length and bytes
+    (block.go:96-111), so a file with its chain's IDs equals the stored one and
+    none of its data blocks is fetched.  Any other file (changed, or stored
+    with other cuts) goes through the byte comparison above, in one call, so
+    the answer never rests on how the stored chain was cut.  The result is
+    that of ``by_id=False`` plus ``"matched_by_id"``, the number of files
+    settled without their blocks.
 
     Returns ``{"files", "directories", "different"}``: the files and
     directories compared, and one ``(path, reason)`` per path that differs.
@@ -583,17 +640,36 @@ def diff_tree(eng: Engine, root_entry: FileEntry, read_block, local_root, window
                     differs(os.path.join(local, name), "remote path does not exist")
             level.extend((kid, local) for kid in kids)
     ids = _file_chains(eng, read_block, [e for e, _ in data_files])
-    if data_files:
-        res = eng._restore_files_stream(ids, lambda f, i: read_block(ids[f][i])[:2], None,
-                                        [p for _, p in data_files],
-                                        [max(int(e.file_size), 0) for e, _ in data_files], window_bytes, io_threads, None)
-        for (e, local), r, chain in zip(data_files, res, ids):
+    rest = list(range(len(data_files)))  # the files whose bytes are compared
+    why: Dict[int, str] = {}             # a file's data reason, reported in the files' order below
+    if by_id:
+        out["matched_by_id"] = 0
+    if by_id and data_files:
+        ms = eng.match_paths([p for _, p in data_files], ids, io_threads=io_threads,
+                             sizes=[int(e.file_size) for e, _ in data_files], skip_unreadable=True)
+        rest = []
+        for k, m in enumerate(ms):
+            if m.errno:
+                why[k] = f"cannot read the local file: {os.strerror(m.errno)}"
+            elif m.same:
+                out["matched_by_id"] += 1
+            else:
+                rest.append(k)
+    if rest:
+        res = eng._restore_files_stream([ids[k] for k in rest], lambda f, i: read_block(ids[rest[f]][i])[:2], None,
+                                        [data_files[k][1] for k in rest],
+                                        [max(int(data_files[k][0].file_size), 0) for k in rest], window_bytes,
+                                        io_threads, None)
+        for k, r in zip(rest, res):
+            local, chain = data_files[k][1], ids[k]
             if r.bad_index is not None:
                 raise HbxError(f"block {chain[r.bad_index].hex()} (block {r.bad_index} of {os.fsdecode(local)}) "
                                f"corrupted (status {r.bad_status})")
             if r.errno:
-                differs(local, f"cannot read the local file: {os.strerror(r.errno)}")
+                why[k] = f"cannot read the local file: {os.strerror(r.errno)}"
             elif r.first_diff is not None:
-                differs(local, f"data is different at offset {r.first_diff}")
+                why[k] = f"data is different at offset {r.first_diff}"
+    for k in sorted(why):
+        differs(data_files[k][1], why[k])
     out["different"] = [(os.fsdecode(p), "; ".join(reasons[p])) for p in order]
     return out

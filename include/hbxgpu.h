@@ -887,6 +887,76 @@ int hbx_restore_files_stream(hbx_ctx *ctx, uint64_t n_files, const uint64_t *fir
                              uint64_t window_bytes, const char *const *out_paths, const char *const *local_paths,
                              uint32_t io_threads, uint64_t max_block, hbx_restored_file *results);
 
+/* ---- Diff and restore by block ID: local files against stored chains (K12) -----
+ * diffEntry / diffFileData (hashback/restore.go:249-277, 317-367) fetch, verify
+ * and compare every data block of every file whose size matches.  A file's
+ * stored chain is its list of block IDs, and a block ID binds the block's
+ * length and bytes (block.go:96-111): if cutting and hashing the LOCAL file
+ * gives the same ID list, the file equals the stored one and none of its data
+ * blocks needs to come off the wire.  The converse does not hold: a chain cut
+ * by another chunker names equal bytes with other IDs, so a file that is not
+ * `same` goes to the byte comparison (hbx_restore_files_stream in diff mode);
+ * it is never reported as different on the strength of its IDs.
+ * K12 (hbx_k12_chain_match) compares, per file, the local ID list with the
+ * expected one: one wave per file, a 32-byte record per file. */
+typedef struct {
+  uint32_t n_match;     /* length of the common prefix of the local and the expected ID list */
+  uint32_t n_local;     /* chunks the local file was cut into */
+  uint32_t n_expect;    /* IDs in the expected chain */
+  uint32_t same;        /* 1 iff n_match == n_local == n_expect */
+  uint64_t match_bytes; /* local offset where chunk n_match starts: cut_ends[n_match - 1], 0 for n_match == 0
+                           (so the file's length when n_match == n_local) */
+  uint64_t reserved;    /* 0 */
+} hbx_chain_match;
+/* Short-cuts diffFileData / diffEntry (restore.go:249-277, 317-367) for ID lists
+ * the caller already holds, in host memory: file f's local IDs are
+ * local_ids[16 local_first[f] .. 16 local_first[f + 1]), its expected chain
+ * expect_ids[16 expect_first[f] .. 16 expect_first[f + 1]) (*_first: n_files + 1
+ * running counts from 0).  local_cut_ends (parallel to local_ids) may be NULL:
+ * match_bytes is then 0.  match receives n_files records.  Runs K12 alone, as
+ * hbx_idset_insert runs K9 alone.  Synchronous; HBX_ERR_STATE while batches are
+ * pending; n_files == 0 is HBX_OK.  HBX_ERR_ARG: a NULL context, array or
+ * match, running counts that decrease, a chain of 2^32 or more IDs, 2^32 or
+ * more local IDs in all. */
+int hbx_match_chains(hbx_ctx *ctx, uint64_t n_files, const uint64_t *local_first, const uint8_t *local_ids,
+                     const uint64_t *local_cut_ends, const uint64_t *expect_first, const uint8_t *expect_ids,
+                     hbx_chain_match *match);
+/* hbx_submit_device with expected chains: short-cuts diffFileData / diffEntry
+ * (restore.go:249-277, 317-367) for files in device memory.  expect_first ==
+ * NULL is exactly hbx_submit_device.  Otherwise expect_first (n_files + 1
+ * running counts, expect_first[0] need not be 0) and the IDs they index are
+ * copied at submit (the caller's arrays are free on return), K12 runs on the
+ * device once the batch's last chain is hashed, and match[f] (required; valid
+ * until then) is filled by the hbx_wait that completes the batch.
+ * VERDICT-ONLY mode: cut_ends, ids, out_base and caps all NULL together.  The
+ * result slots are sized by hbx_max_chunks(len), and the batch brings back only
+ * its per-file sections (content IDs, content types, match records: at most
+ * 52 n_files + 768 bytes) instead of 24 bytes per result slot; summaries
+ * (may be NULL) are filled as usual.
+ * HBX_ERR_ARG: a NULL context; expect_first without match; expect_first
+ * without expect_ids while the chains hold an ID; running counts that
+ * decrease; a chain of 2^32 or more IDs; only some of cut_ends, ids, out_base
+ * and caps NULL (out_base and caps are required unless all four are NULL;
+ * without expect_first they are always required).  Verify batches and segment
+ * batches take no match; match together with an ID set is not offered. */
+int hbx_submit_device_match(hbx_ctx *ctx, const void *d_arena, uint64_t n_files, const uint64_t *file_offs,
+                            const uint64_t *file_lens, uint64_t *cut_ends, uint8_t *ids, const uint64_t *out_base,
+                            const uint64_t *caps, hbx_file_summary *summaries, const uint64_t *expect_first,
+                            const uint8_t *expect_ids, hbx_chain_match *match);
+/* hbx_store_paths_status (without compression) with expected chains: short-cuts
+ * diffFileData / diffEntry (restore.go:249-277, 317-367) for files on disk, at
+ * the store path's speed.  expect_first == NULL is exactly
+ * hbx_store_paths_status without compression, except that status may be NULL
+ * (every read failure then fails the call, as in hbx_store_paths_dd).  A file
+ * with a non-zero status has n_local 0; its record means nothing more.
+ * batch_bytes is honoured down to 1 MiB, as with a set; the records do not
+ * depend on how the files fall into batches.  Verdict-only mode and the
+ * argument checks as hbx_submit_device_match. */
+int hbx_store_paths_match(hbx_ctx *ctx, uint64_t n_files, const char *const *paths, const uint64_t *lens,
+                          uint64_t *cut_ends, uint8_t *ids, const uint64_t *out_base, const uint64_t *caps,
+                          hbx_file_summary *summaries, int32_t *status, uint32_t io_threads, uint64_t batch_bytes,
+                          const uint64_t *expect_first, const uint8_t *expect_ids, hbx_chain_match *match);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
@@ -916,7 +986,10 @@ int hbx_free_pinned(void *p);
  * hbx_restore_* call spent staging its input, inflating, verifying beside
  * K10 / K11, and copying out, each phase ending on a synchronization;
  * restore_many: the staged windows, K11 passes and streams inflated again of
- * the latest hbx_restore_files_* call.  No reference counterpart: diagnostics. */
+ * the latest hbx_restore_files_* call; match_push_bytes: the total bytes of
+ * the result pushes of match batches (hbx_submit_device_match,
+ * hbx_store_paths_match) since the context was created.  No reference
+ * counterpart: diagnostics. */
 int hbx_knobs(hbx_ctx *ctx, char *out, uint64_t cap);
 
 /* Device time (ms) of the last completed batch per stage:
