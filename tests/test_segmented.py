@@ -17,6 +17,8 @@ import pytest
 
 from hashbox_amd import _lib
 
+from . import cut_craft
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Mi = 1 << 20
 MIN = 64 * 1024
@@ -38,6 +40,10 @@ CASES = {
     "random_40Mi+1": ("random11", 40 * Mi + 1, 16 * Mi, 13, [3, 1, 1, 3, 5]),
     "random_50Mi+12345": ("random12", 50 * Mi + 12345, 24 * Mi + 4096, 16, [4, 4, 8]),
     "tiled_36Mi+777": ("tiled5", 36 * Mi + 777, 16 * Mi, 6, [2, 1, 1, 2]),
+    # zeros with designed cuts (tests/cut_craft.py SEG_FILES; what each achieves: CRAFTED below)
+    "craft_exact": ("craft_exact", 24 * Mi + 3 * MIN, 16 * Mi, 6, [2, 1, 3]),
+    "craft_slice": ("craft_slice", 26 * Mi + 5, 16 * Mi, 6, [2, 2, 2]),
+    "craft_skew": ("craft_skew", 26 * Mi + 5, 16 * Mi + 48, 6, [2, 2, 2]),
 }
 
 
@@ -46,6 +52,10 @@ def make_input(O, kind: str, n: int) -> np.ndarray:
         return np.zeros(n, np.uint8)
     if kind.startswith("random"):
         return O.random_bytes(n, int(kind[6:]))
+    if kind.startswith("craft"):
+        size, build, _ = cut_craft.SEG_FILES[kind]
+        assert size == n
+        return build()
     assert kind == "tiled5"
     tile = O.random_bytes(4096, 5)
     return np.tile(tile, n // 4096 + 1)[:n].copy()
@@ -183,3 +193,53 @@ def test_segment_rule_equals_whole_file(oracle, whole, name):
     assert np.array_equal(cuts, want.cut_ends)
     assert got_per_seg == per_seg
     assert sum(per_seg) == chunks
+
+
+# what the crafted files are designed to achieve, per chunk: chunk index ->
+# (segment it is cut in, properties); a chunk's slices are relative to the
+# arena of the segment that cuts it
+CRAFTED = {
+    "craft_exact": {1: (0, ["starts at len - MAX: continue", "qb+1 peak in the next segment's bytes"]),
+                    3: (2, ["previous start one past len - MAX: stop and carry", "resumed", "winner at qa = MIN"])},
+    "craft_slice": {2: (1, ["resumed", "winner at slice position 0"]),
+                    4: (2, ["resumed", "winner at slice position 4095"])},
+    "craft_skew": {2: (1, ["resumed", "winner at slice position 0", "arena slices skewed"]),
+                   4: (2, ["resumed", "winner at slice position 4095", "arena slices skewed"])},
+}
+
+
+@pytest.mark.parametrize("name", list(CRAFTED))
+def test_crafted_segment_cases_achieve_what_they_state(oracle, whole, name):
+    kind, n, seg_bytes, _, per_seg = CASES[name]
+    data = make_input(oracle, kind, n)
+    cuts = [int(c) for c in whole(name).cut_ends]
+    assert cuts == list(cut_craft.SEG_FILES[kind][2]), "not the designed cuts"
+    layout = seg_layout(n, seg_bytes)
+    first = np.cumsum([0] + per_seg)  # index of the first chunk each segment cuts
+    D = oracle.digest_all(data)
+    starts = [0] + cuts[:-1]
+    for i, (seg, props) in CRAFTED[name].items():
+        off, ln = layout[seg]
+        assert first[seg] <= i < first[seg + 1]
+        r = cut_craft.Range(D[:off + ln], starts[i], off + ln if seg + 1 < len(layout) else n, off)
+        assert r.cut == cuts[i] and r.tied.size == 1 and r.cut != r.s + r.L
+        for p in props:
+            if p == "resumed":
+                assert i == first[seg] and seg > 0 and 0 < r.s - off <= MAX
+            elif p == "starts at len - MAX: continue":
+                assert r.s - off == ln - MAX and i > first[seg] and seg + 1 < len(layout)
+            elif p == "qb+1 peak in the next segment's bytes":
+                assert r.qb + 1 == off + ln and int(D[r.qb + 1]) > r.max and layout[seg + 1][0] <= r.qb + 1
+            elif p == "previous start one past len - MAX: stop and carry":
+                poff, pln = layout[seg - 1]
+                assert r.s - poff == pln - MAX + 1 and first[seg] == i
+            elif p == "winner at qa = MIN":
+                assert r.win == r.qa == off + MIN
+            elif p == "winner at slice position 0":
+                assert r.pos_of(r.win) == 0
+            elif p == "winner at slice position 4095":
+                assert r.pos_of(r.win) == 4095
+            elif p == "arena slices skewed":
+                assert off % cut_craft.SLICE == 48 * seg and r.win % cut_craft.SLICE != r.pos_of(r.win)
+            else:
+                raise AssertionError(p)
