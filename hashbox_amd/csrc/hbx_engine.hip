@@ -1980,8 +1980,17 @@ void hbx_ctx_destroy(hbx_ctx* c) {
 // Failures of calls made without a context (hbx_plan_pipeline with ctx NULL)
 // are described per thread.
 static thread_local std::string g_noctx_err;
+// A context's text is written under its lock by whichever thread fails a call
+// there, so it is read under that lock too, into a copy of the calling
+// thread's: another thread failing a call meanwhile can neither tear the text
+// nor free it under the reader (tests/test_gpu_threads.py has four threads
+// failing calls on one context).  The copy lives until this thread asks again.
 const char* hbx_last_error(const hbx_ctx* c) {
-  return c ? c->err.c_str() : g_noctx_err.empty() ? "null context" : g_noctx_err.c_str();
+  if (!c) return g_noctx_err.empty() ? "null context" : g_noctx_err.c_str();
+  static thread_local std::string mine;
+  std::lock_guard<std::mutex> g(const_cast<hbx_ctx*>(c)->mu);
+  mine = c->err;
+  return mine.c_str();
 }
 
 int hbx_set_tile_iters(hbx_ctx* c, uint32_t iters) {

@@ -46,7 +46,16 @@
  *     pointers).
  *   - One context = one GPU and its own HIP streams.  Calls on one context are
  *     serialised by an internal lock; use one context per GPU (or per
- *     goroutine) to run in parallel.
+ *     goroutine) to run in parallel.  A context is safe to call from many
+ *     threads, and distinct contexts run concurrently.  hbx_wait completes
+ *     batches in submit order whichever thread calls it.  The text of
+ *     hbx_last_error(ctx) is per context: with several threads on one context
+ *     it may describe another thread's failure, so judge a call by its status
+ *     and read the text right after it for diagnostics only.  The call takes
+ *     the context's lock (it waits for a call in progress there, and must not
+ *     be made from a callback) and returns a copy that stays valid until the
+ *     calling thread's next hbx_last_error.  hbx_last_error(NULL) is per
+ *     calling thread.
  *   - Block IDs are 16 raw MD5 bytes, exactly Go's core.Byte128 (core.go:26).
  *   - cut_ends[i] is the file offset where chunk i ends (exclusive); chunk i
  *     starts at cut_ends[i-1] (0 for i = 0).
@@ -143,7 +152,8 @@ int hbx_pending(hbx_ctx *ctx);
  * launch per batch); a chain takes the part short of a whole slice in its
  * first launch and whole slices after.  A submitted batch is complete after join lag (below)
  * + ceil(min(longest file, 8 MiB)/64 / blocks) - 1 further launches; results are
- * identical for every setting. */
+ * identical for every setting.  Fails with HBX_ERR_STATE while batches are
+ * pending (their launch counts were fixed at submit). */
 int hbx_set_md5_slice(hbx_ctx *ctx, uint32_t blocks);
 /* Reuse the input memory of the OLDEST pending batch: order the engine's
  * next input copies (hbx_memcpy_h2d_async) and submitted batches (chunking

@@ -95,6 +95,11 @@ def test_plain_c_driver_links_and_reports_no_device(tmp_path):
     r = subprocess.run([str(tmp_path / "abi_driver"), str(f), "--expect-nodev"], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout.strip().splitlines()[-1] == "nodev ok", (r.returncode, r.stdout, r.stderr)
     assert r.stdout.startswith("plan R=") and " lag=2 lead=3 period=4 " in r.stdout
+    # the threaded driver (pthreads + the header, as cgo calls from goroutines): two threads get a status
+    # from every call, and each reads its own text from hbx_last_error(NULL)
+    r = subprocess.run([str(tmp_path / "abi_threads"), str(f), "--expect-nodev"], capture_output=True, text=True,
+                       timeout=60)
+    assert r.returncode == 0 and r.stdout.strip().splitlines() == ["nodev ok"], (r.returncode, r.stdout, r.stderr)
 
 
 def test_md5_argument_checks_without_device():

@@ -89,6 +89,41 @@ def test_shared_first_eight_bytes(make_set):
     assert {r.tobytes() for r in s.export()} == set(model)
 
 
+def test_one_home_slot_across_workgroups(make_set):
+    """4,096 distinct IDs with one LE64(id[0..8]): one home slot in the set
+    (16,384 slots) and one in the mark's scratch table, so both probe runs are
+    4,096 long.  Each ID occurs three times in one insert of 12,288, once in
+    each third under another permutation: the three copies always lie in three
+    different 256-thread workgroups of the mark (16 workgroups per third)."""
+    n = 4096
+    base = _random_ids(1, 9)[0]
+    ids = np.repeat(base[None, :], n, axis=0)
+    ids[:, 8:] = np.random.Generator(np.random.PCG64(10)).permutation(1 << 16)[:n].astype("<u8").view(np.uint8) \
+        .reshape(n, 8)
+    assert len({r.tobytes() for r in ids}) == n and len({r[:8].tobytes() for r in ids}) == 1
+    g = np.random.Generator(np.random.PCG64(11))
+    where = np.stack([g.permutation(n) + k * n for k in range(3)], axis=1)  # [id, copy] -> index in the call
+    assert len({tuple(sorted(set((where[j] // 256).tolist()))) for j in range(n)}) > 1
+    assert all(len(set((where[j] // 256).tolist())) == 3 for j in range(n))
+    call = np.zeros((3 * n, 16), np.uint8)
+    for k in range(3):
+        call[where[:, k]] = ids
+    s = make_set(2 * n)
+    assert s.slots == 4 * n
+    model = {}
+    want = _model_insert(model, call)
+    assert int(want.sum()) == n and want[:n].all() and not want[n:].any()
+    assert np.array_equal(s.insert(call), want)
+    assert (s.count, s.dropped) == (n, 0)
+    assert s.contains(ids).all()
+    order = s.export()
+    assert {r.tobytes() for r in order} == set(model)
+    s.truncate(1000)
+    assert s.count == 1000
+    assert s.contains(order[:1000]).all() and not s.contains(order[1000:]).any()
+    assert np.array_equal(s.export(), order[:1000])
+
+
 def test_all_zero_and_all_ff_are_ordinary_keys(make_set):
     s = make_set(16)
     ids = _ids([bytes(16), b"\xff" * 16])
