@@ -43,6 +43,7 @@ EXPORTS = [
     "hbx_restore_in_bound", "hbx_restore_blocks", "hbx_restore_file_stream",
     "hbx_restore_many_window", "hbx_restore_files_blocks", "hbx_restore_files_stream",
     "hbx_match_chains", "hbx_submit_device_match", "hbx_store_paths_match",
+    "hbx_k1_summaries",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -200,6 +201,7 @@ def load() -> ctypes.CDLL:
     L.hbx_input_fence.argtypes = [P, P]
     L.hbx_set_k3_probe.argtypes = [P, I]
     L.hbx_k3_wave_times.argtypes = [P, P, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    L.hbx_k1_summaries.argtypes = [P, P, P, U64, ctypes.POINTER(U64), P, U64, ctypes.POINTER(U64)]
     L.hbx_knobs.argtypes = [P, ctypes.c_char_p, U64]
     L.hbx_stage_totals.argtypes = [P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(U64), I]
     L.hbx_io_times.argtypes = [P, ctypes.POINTER(ctypes.c_double), I]

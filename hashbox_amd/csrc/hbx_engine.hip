@@ -372,6 +372,10 @@ struct hbx_ctx {
   int ssum_slot = 0;
   hipEvent_t ssum_free[2] = {nullptr, nullptr};  // recorded after the K2 that last read the slot
   bool ssum_used[2] = {false, false};
+  // hbx_k1_summaries: the slot the latest synchronous batch's K1 wrote (-1: none, or overwritten since) and
+  // its slices; the per-file bases are still h_slice_base
+  int k1_sum_slot = -1;
+  uint64_t k1_sum_slices = 0;
   // K3 launch orders (triple-buffered by launch index % 3): plan j (scan
   // stream) writes order[j%3] from order[(j-1)%3]; K3 j (hash stream) reads it
   DevBuf d_order[3], d_octl[3], d_q[3];  // (+ K3Q's item queue per slot)
@@ -1176,6 +1180,7 @@ int submit_batch_timed(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64
                        const uint64_t* seg_offs, hbx_idset* set, uint8_t* fresh, const MatchIn* mi) {
   g_slow.mark(0);
   g_slow.clear();
+  c->k1_sum_slot = -1;  // h_slice_base and a summary slot are about to be rewritten
   if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
   if (n > 0xFFFFFFFFull) return c->fail(HBX_ERR_ARG, "too many files");
   for (uint64_t f = 0; f < n; f++)
@@ -1711,9 +1716,18 @@ int wait_oldest(hbx_ctx* c) {
 int run_device_sync(hbx_ctx* c, const void* d_arena, uint64_t n, const uint64_t* offs,
                     const uint64_t* lens, uint64_t* cut_ends, uint8_t* ids,
                     const uint64_t* out_base, const uint64_t* caps, hbx_file_summary* sums) {
+  const int slot = c->ssum_slot;  // the summary slot this batch's K1 writes
   int rc = submit_batch(c, d_arena, n, offs, lens, cut_ends, ids, out_base, caps, sums, kBudgetAll);
   if (rc) return rc;
-  return wait_oldest(c);
+  rc = wait_oldest(c);
+  if (rc == HBX_OK || rc == HBX_ERR_CAPACITY) {  // the scan ran whole either way: hbx_k1_summaries may read it
+    uint64_t slices = 0;
+    for (uint64_t f = 0; f < n; f++)
+      if (scan_iters(lens[f])) slices += (lens[f] + kSlice - 1) / kSlice;
+    c->k1_sum_slot = slot;
+    c->k1_sum_slices = slices;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -2167,6 +2181,31 @@ int hbx_k3_wave_times(hbx_ctx* c, uint64_t* out, uint32_t max_waves, uint32_t* n
   return HBX_OK;
 }
 
+int hbx_k1_summaries(hbx_ctx* c, uint64_t* first, uint64_t* count, uint64_t max_files, uint64_t* n_files,
+                     uint32_t* pairs, uint64_t max_slices, uint64_t* n_slices) {
+  if (!c || !n_files || !n_slices) return HBX_ERR_ARG;
+  if ((max_files && (!first || !count)) || (max_slices && !pairs)) return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  *n_files = 0;
+  *n_slices = 0;
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->k1_sum_slot < 0)
+    return c->fail(HBX_ERR_STATE, "no synchronous device batch since the context was created, reserved or last submitted to");
+  const uint64_t n = c->h_slice_base.size(), slices = c->k1_sum_slices;
+  *n_files = n;
+  *n_slices = slices;
+  if (max_files < n || max_slices < slices) return c->fail(HBX_ERR_CAPACITY, "hbx_k1_summaries: output arrays too small");
+  for (uint64_t f = 0; f < n; f++) {
+    first[f] = c->h_slice_base[f];
+    count[f] = (f + 1 < n ? c->h_slice_base[f + 1] : slices) - c->h_slice_base[f];
+  }
+  if (!slices) return HBX_OK;
+  HBX_TRY(c, hipSetDevice(c->device));
+  // the batch was collected, so its K1 and K2 are complete; the dummy slot behind the last slice is left out
+  HBX_TRY(c, hipMemcpy(pairs, c->d_ssum[c->k1_sum_slot].p, slices * sizeof(uint2), hipMemcpyDeviceToHost));
+  return HBX_OK;
+}
+
 int hbx_stage_times(hbx_ctx* c, float ms[5]) {
   if (!c || !ms) return HBX_ERR_ARG;
   std::lock_guard<std::mutex> g(c->mu);
@@ -2195,6 +2234,7 @@ int reserve_locked(hbx_ctx* c, uint32_t batches, uint64_t files, uint64_t bytes,
                    uint64_t match_ids) {
   if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
   HBX_TRY(c, hipSetDevice(c->device));
+  c->k1_sum_slot = -1;  // the summary slots may be reallocated
   const uint64_t caps = bytes / HBX_MIN_BLOCK_SIZE + files;  // >= sum of max_chunks over the files
   const uint64_t tiles = bytes / ((uint64_t)(c->tile_iters ? c->tile_iters : kTileItersMin) * HBX_MIN_BLOCK_SIZE) + files;
   const uint64_t slices = bytes / kSlice + files;

@@ -695,6 +695,21 @@ class Engine:
         self._check(self._L.hbx_k3_wave_times(self._ctx, _p(out), n.value, ctypes.byref(n)), "hbx_k3_wave_times")
         return out[:n.value]
 
+    def k1_summaries(self):
+        """Diagnostics: the slice summaries K1 stored for the latest
+        synchronous device batch (hbx_k1_summaries).  Returns (first, count,
+        pairs): per file its first slice and slice count, and pairs[j] =
+        (smax, sprev) of slice j, uint32, shape (slices, 2)."""
+        nf, ns = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self._L.hbx_k1_summaries(self._ctx, None, None, 0, ctypes.byref(nf), None, 0, ctypes.byref(ns))
+        if rc != _lib.ERR_CAPACITY:
+            self._check(rc, "hbx_k1_summaries")
+        first, count = np.zeros(max(nf.value, 1), np.uint64), np.zeros(max(nf.value, 1), np.uint64)
+        pairs = np.zeros((max(ns.value, 1), 2), np.uint32)
+        self._check(self._L.hbx_k1_summaries(self._ctx, _p(first), _p(count), nf.value, ctypes.byref(nf), _p(pairs),
+                                             ns.value, ctypes.byref(ns)), "hbx_k1_summaries")
+        return first[:nf.value], count[:nf.value], pairs[:ns.value]
+
     def knobs(self) -> dict:
         """The context's effective pipeline knobs (hbx_knobs), including
         whether HBX_* A/B switches were honoured (only with HBX_AB=1)."""

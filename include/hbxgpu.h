@@ -1032,6 +1032,29 @@ int hbx_set_k3_probe(hbx_ctx *ctx, int on);
  * wave, up to max_waves) after the hash stream drains; *n_waves = waves per
  * launch. */
 int hbx_k3_wave_times(hbx_ctx *ctx, uint64_t *out, uint32_t max_waves, uint32_t *n_waves);
+/* Diagnostics: the slice summaries K1 stored for the context's most recent
+ * synchronous device batch (hbx_chunk_hash_device, hbx_chunk_hash_batch and
+ * hbx_chunk_hash through it), copied from device memory.  K1 summarises every
+ * 4,096 window positions of a file that has split candidates: a file of
+ * len > 2 * HBX_MIN_BLOCK_SIZE has ceil(len / 4096) slices, any other file
+ * none.  first[f] / count[f] (max_files entries each): file f's first slice
+ * and its slice count in `pairs`, in the batch's file order.  pairs
+ * (2 x uint32 per slice, max_slices slices): for slice j of a file, D(q) the
+ * window digest of the 65,536 bytes ending at file position q (virtual zero
+ * bytes before the file start),
+ *   word 0  smax  = max D(q) over q in [4096 j, min(4096 (j + 1), len)),
+ *   word 1  sprev = D(4096 j - 1), the digest K2 starts a re-scan of the
+ *                   slice from; 0x80000000 for j == 0 (no byte rolled in).
+ * *n_files and *n_slices are always set to the batch's counts.  The slot K1
+ * gives the slices past a file's end is not returned.  HBX_ERR_CAPACITY if
+ * max_files or max_slices is smaller than those counts (nothing copied; both
+ * may be 0 with null arrays to ask for the counts), HBX_ERR_STATE while
+ * batches are pending, before any synchronous batch has run, and once a
+ * later submit of any kind or hbx_reserve / hbx_apply_plan may have reused
+ * the summaries' memory; HBX_ERR_ARG for a null ctx, n_files or n_slices, or
+ * a null array with a non-zero capacity.  Changes no result and no knob. */
+int hbx_k1_summaries(hbx_ctx *ctx, uint64_t *first, uint64_t *count, uint64_t max_files, uint64_t *n_files,
+                     uint32_t *pairs, uint64_t max_slices, uint64_t *n_slices);
 /* Tile length of K1 in 64 KiB iterations, 1..1024; 0 (the default) sizes
  * tiles per batch: about two per CU, 16..256 iterations (1-16 MiB). */
 int hbx_set_tile_iters(hbx_ctx *ctx, uint32_t iters);

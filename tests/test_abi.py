@@ -133,3 +133,17 @@ def test_engine_hmac_construction_matches_reference_kats():
     for r in rows:
         assert e.deep_hmac(r["depth"], r["text"].encode(), r["key"].encode()).hex() == r["out"], r
     assert e.deep_hmac(0, b"x", b"k") == bytes(16)  # DeepHmac with depth 0 returns the zero hash
+
+
+def test_k1_summaries_argument_checks_without_device():
+    """hbx_k1_summaries rejects a null context before any HIP call, whatever
+    the other arguments are, and leaves the counts alone."""
+    from hashbox_amd import _lib
+    L = _lib.load()
+    nf, ns = ctypes.c_uint64(7), ctypes.c_uint64(9)
+    buf = (ctypes.c_uint64 * 4)()
+    assert L.hbx_k1_summaries(None, None, None, 0, ctypes.byref(nf), None, 0, ctypes.byref(ns)) == -1
+    assert L.hbx_k1_summaries(None, buf, buf, 2, ctypes.byref(nf), buf, 2, ctypes.byref(ns)) == -1
+    assert L.hbx_k1_summaries(None, None, None, 0, None, None, 0, None) == -1
+    assert (nf.value, ns.value) == (7, 9)
+    assert "hbx_k1_summaries" in _lib.EXPORTS
