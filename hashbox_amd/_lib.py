@@ -43,7 +43,7 @@ EXPORTS = [
     "hbx_restore_in_bound", "hbx_restore_blocks", "hbx_restore_file_stream",
     "hbx_restore_many_window", "hbx_restore_files_blocks", "hbx_restore_files_stream",
     "hbx_match_chains", "hbx_submit_device_match", "hbx_store_paths_match",
-    "hbx_k1_summaries",
+    "hbx_k1_summaries", "hbx_locate_ids",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -130,6 +130,13 @@ class ChainMatch(ctypes.Structure):
                 ("same", ctypes.c_uint32), ("match_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class BlockLoc(ctypes.Structure):
+    """hbx_block_loc: where the pool holds one wanted block ID (K13)."""
+    _fields_ = [("file", ctypes.c_uint32), ("chunk", ctypes.c_uint32), ("off", ctypes.c_uint64),
+                ("len", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+NO_FILE = 0xFFFFFFFF                # hbx_block_loc.file of an ID the pool does not hold
 BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
 MAX_BLOCK = 8 << 20                 # HBX_MAX_BLOCK
 ERR_IO, ERR_VERIFY = -4, -9
@@ -268,6 +275,7 @@ def load() -> ctypes.CDLL:
     L.hbx_match_chains.argtypes = [P, U64, P, P, P, P, P, P]
     L.hbx_submit_device_match.argtypes = L.hbx_submit_device.argtypes + [P, P, P]
     L.hbx_store_paths_match.argtypes = [P, U64, P, P, P, P, P, P, P, P, ctypes.c_uint32, U64, P, P, P]
+    L.hbx_locate_ids.argtypes = [P, U64, P, P, P, U64, P, P, PU64]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

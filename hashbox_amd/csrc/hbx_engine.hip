@@ -42,6 +42,7 @@
 #include "hbx_inflate_split.hip"
 #include "hbx_dedup.hip"
 #include "hbx_match.hip"
+#include "hbx_locate.hip"
 #include "hbx_restore.hip"
 #include "hbx_restore_many.hip"
 #include "hbx_formats.h"
@@ -448,6 +449,8 @@ struct hbx_ctx {
   uint64_t dd_submitted = 0, dd_marked = 0;
   uint64_t match_push_bytes = 0;  // hbx_knobs: bytes of the result pushes of match batches
   DevBuf d_mt[5], d_mtout;        // hbx_match_chains: the two ID lists, their firsts, the cut ends; the records
+  // hbx_locate_ids: the pool's IDs, cut ends and firsts, the wanted IDs, the slot table, the records + hit count
+  DevBuf d_lc[6];
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -1962,6 +1965,7 @@ void hbx_ctx_destroy(hbx_ctx* c) {
   c->d_dscratch.release();
   for (DevBuf& d : c->d_mt) d.release();
   c->d_mtout.release();
+  for (DevBuf& d : c->d_lc) d.release();
   for (hbx_seg* h : c->segs_open) delete h;
   for (DevBuf& d : c->seg_words) d.release();
   c->d_segmsg.release();
@@ -2391,6 +2395,55 @@ int hbx_match_chains(hbx_ctx* c, uint64_t n, const uint64_t* local_first, const 
   HBX_TRY(c, hbxm::match(s, ma));
   HBX_TRY(c, hipMemcpyAsync(match, c->d_mtout.p, n * sizeof(hbx_chain_match), hipMemcpyDeviceToHost, s));
   HBX_TRY(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+int hbx_locate_ids(hbx_ctx* c, uint64_t nf, const uint64_t* pool_first, const uint8_t* pool_ids,
+                   const uint64_t* pool_cut_ends, uint64_t nw, const uint8_t* want_ids, hbx_block_loc* loc,
+                   uint64_t* n_found) {
+  if (!c) return HBX_ERR_ARG;
+  if (nf > 0x7FFFFFFFull || nw > 0xFFFFFFFFull || (nf && !pool_first) || (nw && (!want_ids || !loc)))
+    return HBX_ERR_ARG;
+  for (uint64_t f = 0; f < nf; f++)
+    if (pool_first[f + 1] < pool_first[f]) return HBX_ERR_ARG;
+  const uint64_t p0 = nf ? pool_first[0] : 0, np = nf ? pool_first[nf] - p0 : 0;
+  if (np > hbxd::kMaxMark || (np && (!pool_ids || !pool_cut_ends))) return HBX_ERR_ARG;
+  if (nw == 0) {
+    if (n_found) *n_found = 0;
+    return HBX_OK;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  HBX_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->rstream;
+  // K13 alone, as hbx_match_chains runs K12 alone: the lists staged in device memory, firsts rebased to 0
+  std::vector<uint64_t> first(nf + 1, 0);
+  for (uint64_t f = 0; f <= nf && nf; f++) first[f] = pool_first[f] - p0;
+  const uint64_t slots = hbxd::table_slots(np);
+  HBX_TRY(c, c->d_lc[0].ensure(np * 16));
+  HBX_TRY(c, c->d_lc[1].ensure(np * 8));
+  HBX_TRY(c, c->d_lc[2].ensure((nf + 1) * 8));
+  HBX_TRY(c, c->d_lc[3].ensure(nw * 16));
+  HBX_TRY(c, c->d_lc[4].ensure(slots * sizeof(uint32_t)));
+  HBX_TRY(c, c->d_lc[5].ensure(nw * sizeof(hbx_block_loc) + 8));
+  if (np) {
+    HBX_TRY(c, hipMemcpyAsync(c->d_lc[0].p, pool_ids + 16 * p0, np * 16, hipMemcpyHostToDevice, s));
+    HBX_TRY(c, hipMemcpyAsync(c->d_lc[1].p, pool_cut_ends + p0, np * 8, hipMemcpyHostToDevice, s));
+  }
+  HBX_TRY(c, hipMemcpyAsync(c->d_lc[2].p, first.data(), (nf + 1) * 8, hipMemcpyHostToDevice, s));
+  HBX_TRY(c, hipMemcpyAsync(c->d_lc[3].p, want_ids, nw * 16, hipMemcpyHostToDevice, s));
+  unsigned long long* d_found =
+      reinterpret_cast<unsigned long long*>(c->d_lc[5].as<uint8_t>() + nw * sizeof(hbx_block_loc));
+  const hbxl::Args la{c->d_lc[0].as<uint4>(), c->d_lc[1].as<uint64_t>(), c->d_lc[2].as<uint64_t>(),
+                      c->d_lc[3].as<uint4>(), c->d_lc[4].as<uint32_t>(), c->d_lc[5].as<uint4>(), d_found,
+                      (uint32_t)np, (uint32_t)nw, (uint32_t)nf, (uint32_t)(slots - 1)};
+  HBX_TRY(c, hbxl::locate(s, la));
+  unsigned long long found = 0;
+  HBX_TRY(c, hipMemcpyAsync(loc, c->d_lc[5].p, nw * sizeof(hbx_block_loc), hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipMemcpyAsync(&found, d_found, sizeof(found), hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipStreamSynchronize(s));
+  if (n_found) *n_found = found;
   return HBX_OK;
 }
 

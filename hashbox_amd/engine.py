@@ -333,6 +333,7 @@ class Engine:
         self._pending = deque()
         self.wait_s = 0.0
         self.last_call_s = 0.0
+        self.last_located = 0  # hits of the latest locate_ids (hbx_locate_ids' n_found)
         if tile_iters is not None:
             self._check(self._L.hbx_set_tile_iters(self._ctx, int(tile_iters)), "set_tile_iters")
         if md5_slice is not None:
@@ -545,6 +546,39 @@ class Engine:
                                              _p(cuts) if cuts is not None else None, ef.ctypes.data, _p(eids), rec),
                     "hbx_match_chains")
         return _matches(rec, n)
+
+    def locate_ids(self, pool_ids, pool_cut_ends, want_ids) -> np.ndarray:
+        """K13 alone (hbx_locate_ids): where a pool of local files holds each
+        wanted block ID.  ``pool_ids[f]`` and ``pool_cut_ends[f]`` are pool
+        file f's chunk IDs and cut ends (as FileChunks gives them; lists of
+        16-byte IDs or uint8 [k, 16] arrays), ``want_ids`` a flat list of IDs.
+        Returns a structured array of one record per wanted ID (``file``,
+        ``chunk``, ``off``, ``len``): the pool file with the lowest pool
+        position that holds the ID, the chunk's index in it, where it starts
+        and how long it is; ``file == 0xFFFFFFFF`` for an ID the pool does not
+        hold.  A located chunk is a candidate, not a fact: the file may have
+        changed since it was hashed, so its bytes go through VerifyBlock
+        (:meth:`restore_files` with a raw block) before they are used."""
+        if len(pool_ids) != len(pool_cut_ends):
+            raise ValueError("one list of cut ends per pool file")
+        nf = len(pool_ids)
+        pf, pids = _chain_lists(pool_ids)
+        cuts = np.ascontiguousarray(np.concatenate([np.asarray(c, np.uint64).reshape(-1) for c in pool_cut_ends])
+                                    if nf else np.zeros(0, np.uint64), np.uint64)
+        if cuts.shape[0] != pids.shape[0]:
+            raise ValueError("one cut end per pool ID")
+        want = _ids_array(want_ids) if len(want_ids) else np.zeros((0, 16), np.uint8)
+        nw = want.shape[0]
+        rec = (_lib.BlockLoc * max(nw, 1))()
+        found = ctypes.c_uint64(0)
+        self._check(self._L.hbx_locate_ids(self._ctx, nf, pf.ctypes.data, _p(pids), _p(cuts), nw, _p(want), rec,
+                                           ctypes.byref(found)), "hbx_locate_ids")
+        self.last_located = int(found.value)
+        v = np.ctypeslib.as_array(rec)[:nw]
+        out = np.empty(nw, np.dtype([("file", np.uint32), ("chunk", np.uint32), ("off", np.uint64), ("len", np.uint64)]))
+        for name in out.dtype.names:
+            out[name] = v[name]
+        return out
 
     def match_paths(self, paths: Sequence[Union[str, os.PathLike]], chains_ids, io_threads: int = 16,
                     batch_bytes: int = 1 << 30, sizes: Optional[Sequence[int]] = None,

@@ -368,11 +368,61 @@ def _create_file(local: bytes, e: FileEntry) -> int:
     return mode
 
 
+_REUSE_FDS = 32  # pool files kept open at a time while their chunks are read back
+
+
+def _sibling_temporary(local: bytes, e: FileEntry) -> Tuple[bytes, int]:
+    """A fresh file beside ``local``, created with the entry's mode and O_EXCL,
+    and the mode it got.  By the time this is called every entry of the
+    directory exists on disk, so a name O_EXCL accepts is no entry's."""
+    d = os.path.dirname(local)
+    while True:
+        tmp = os.path.join(d, b".hbx-restore-" + os.urandom(8).hex().encode() + b".tmp")
+        try:
+            fd = os.open(tmp, os.O_CREAT | os.O_EXCL | os.O_WRONLY, e.file_mode & 0o777)
+        except FileExistsError:
+            continue
+        mode = stat.S_IMODE(os.fstat(fd).st_mode)
+        os.close(fd)
+        return tmp, mode
+
+
+class _PoolReader:
+    """Chunks of the pool's files read back by (file, offset, length), with a
+    bounded number of descriptors open.  None for anything but the whole chunk:
+    that block is then fetched."""
+
+    def __init__(self, paths: Sequence[bytes]):
+        self.paths = paths
+        self.fds: Dict[int, int] = {}  # insertion order = least recently used first
+
+    def read(self, f: int, off: int, n: int) -> Optional[bytes]:
+        try:
+            fd = self.fds.pop(f, None)
+            if fd is None:
+                if len(self.fds) >= _REUSE_FDS:
+                    os.close(self.fds.pop(next(iter(self.fds))))
+                fd = os.open(self.paths[f], os.O_RDONLY)
+            self.fds[f] = fd
+            data = os.pread(fd, n, off)
+        except OSError:
+            return None
+        return data if len(data) == n else None
+
+    def close(self):
+        for fd in self.fds.values():
+            os.close(fd)
+        self.fds = {}
+
+
 def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: bytes, window_bytes: int,
-                          io_threads: int, keep_matching: bool = False) -> Dict[str, int]:
+                          io_threads: int, keep_matching: bool = False, reuse_local: bool = False,
+                          reuse_paths: Sequence = ()) -> Dict[str, int]:
     stats = {"files": 0, "directories": 0, "bytes": 0}
-    if keep_matching:
+    if keep_matching or reuse_local:
         stats["kept"] = 0
+    if reuse_local:
+        stats.update(blocks_reused=0, bytes_reused=0, blocks_fetched=0, reuse_retried=0)
     made_dirs: List[Tuple[bytes, int]] = []
     # entry, local path, the mode its creation gave it (None: a keep_matching candidate, not created yet)
     files: List[Tuple[FileEntry, bytes, Optional[int]]] = []
@@ -398,17 +448,21 @@ def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: 
                     raise HbxError(f"invalid ContentType for a file ({e.content_type})")
                 # keep_matching: a regular file of the entry's size already there is neither created nor
                 # truncated until its block IDs have been compared with its chain
+                # (reuse_local: of any size, and it stays as it is until its replacement is complete)
                 candidate = False
-                if keep_matching and int(e.file_size) > 0 and e.content_type != TYPE_EMPTY:
+                if (keep_matching or reuse_local) and int(e.file_size) > 0 and e.content_type != TYPE_EMPTY:
                     try:
                         st = os.lstat(local)
-                        candidate = stat.S_ISREG(st.st_mode) and st.st_size == int(e.file_size)
+                        candidate = stat.S_ISREG(st.st_mode) and (reuse_local or st.st_size == int(e.file_size))
                     except OSError:
                         pass
                 files.append((e, local, None if candidate else _create_file(local, e)))
         blocks = _read_verified_many(eng, read_block, [e.content_block_id for e, _ in want], "directory")
         level = [(kid, local) for (_, local), blk in zip(want, blocks) for kid in parse_directory_block(blk)]
     ids = _file_chains(eng, read_block, [e for e, _, _ in files])
+    if reuse_local:
+        _restore_reusing(eng, read_block, files, ids, stats, window_bytes, io_threads, reuse_paths)
+        return _finish_tree(files, made_dirs, stats)
     kept = set()
     cand = [k for k in range(len(files)) if files[k][2] is None]
     if cand:
@@ -446,6 +500,10 @@ def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: 
         if r.errno:
             raise HbxError(f"cannot write {os.fsdecode(files[k][1])}: {os.strerror(r.errno)}")
         stats["bytes"] += r.bytes
+    return _finish_tree(files, made_dirs, stats)
+
+
+def _finish_tree(files, made_dirs, stats) -> Dict[str, int]:
     now = time.time_ns()
     for e, local, _ in files:
         os.utime(local, ns=(now, int(e.mod_time)))
@@ -455,8 +513,143 @@ def _restore_tree_batched(eng: Engine, root_entry: FileEntry, read_block, dest: 
     return stats
 
 
+def _restore_reusing(eng: Engine, read_block, files, ids, stats, window_bytes: int, io_threads: int,
+                     reuse_paths: Sequence):
+    """The data of ``files`` (entry, local path, mode or None for a regular
+    file that was there before the walk and has not been touched) with every
+    block that some local file already holds taken from that file."""
+    cand = [k for k in range(len(files)) if files[k][2] is None]
+    # the pool: the files that were there, and what the caller adds (read only)
+    pool_paths = [files[k][1] for k in cand]
+    pool_sizes = []
+    for p in list(pool_paths):
+        try:
+            pool_sizes.append(os.lstat(p).st_size)
+        except OSError:
+            pool_sizes.append(0)  # (gone since the walk: unreadable below)
+    seen = set(pool_paths)
+    for p in reuse_paths:
+        p = os.fsencode(os.fspath(p))
+        try:
+            st = os.stat(p)
+        except OSError:
+            continue
+        if stat.S_ISREG(st.st_mode) and p not in seen:
+            seen.add(p)
+            pool_paths.append(p)
+            pool_sizes.append(st.st_size)
+    kept = set()
+    src_paths: List[bytes] = []
+    src_ids, src_cuts = [], []
+    if pool_paths:
+        # cut and hashed at the store path's speed: a candidate whose block IDs are its chain's is already
+        # right (keep_matching); every readable file's chunks are where wanted blocks may be found
+        ms = eng.match_paths(pool_paths, [ids[k] for k in cand] + [[]] * (len(pool_paths) - len(cand)),
+                             io_threads=io_threads, sizes=pool_sizes, skip_unreadable=True, chunks=True)
+        umask = os.umask(0)
+        os.umask(umask)
+        for n, m in enumerate(ms):
+            if n < len(cand) and m.same and not m.errno:
+                e, local, _ = files[cand[n]]
+                kept.add(cand[n])
+                os.chmod(local, e.file_mode & 0o777 & ~umask)  # what creating it would have given it
+            if not m.errno and m.chunks is not None and m.chunks.n_chunks:
+                src_paths.append(pool_paths[n])
+                src_ids.append(m.chunks.ids)
+                src_cuts.append(m.chunks.cut_ends)
+    stats["kept"] = len(kept)
+    for k in cand:  # (a chain without blocks: nothing to reuse, created empty as ever)
+        if k not in kept and not ids[k]:
+            files[k] = (files[k][0], files[k][1], _create_file(files[k][1], files[k][0]))
+    with_data = [k for k in range(len(files)) if ids[k] and k not in kept]
+    if not with_data:
+        return
+    first = np.zeros(len(with_data) + 1, np.int64)
+    first[1:] = np.cumsum([len(ids[k]) for k in with_data])
+    loc = eng.locate_ids(src_ids, src_cuts, [i for k in with_data for i in ids[k]])
+    loc_file, loc_off, loc_len = loc["file"].tolist(), loc["off"].tolist(), loc["len"].tolist()
+    pool = _PoolReader(src_paths)
+    temps: Dict[int, bytes] = {}  # a file that was there is written beside itself and renamed when it is good
+    try:
+        out_paths = []
+        for k in with_data:
+            e, local, mode = files[k]
+            if mode is None:
+                temps[k], mode = _sibling_temporary(local, e)
+                files[k] = (e, local, mode)
+            out_paths.append(temps.get(k, local))
+        # (a mode without the owner's write bit, 0444: writable while written, as in the unbatched path)
+        locked = [n for n, k in enumerate(with_data) if not files[k][2] & stat.S_IWUSR]
+        for n in locked:
+            os.chmod(out_paths[n], files[with_data[n]][2] | stat.S_IWUSR)
+        hints = [max(int(files[k][0].file_size), 0) for k in with_data]
+
+        def run(sel: List[int], reuse: bool):
+            """restore_files over with_data[n] for n in sel; per file the indices of its reused blocks."""
+            reused: List[Dict[int, int]] = [{} for _ in sel]
+
+            def source(f: int, i: int):
+                n = sel[f]
+                j = int(first[n]) + i
+                if reuse and loc_file[j] != _lib.NO_FILE:
+                    data = pool.read(loc_file[j], loc_off[j], loc_len[j])
+                    if data is not None:
+                        reused[f][i] = len(data)
+                        return _lib.BLOCK_RAW, data
+                stats["blocks_fetched"] += 1
+                return read_block(ids[with_data[n]][i])[:2]
+
+            res = eng.restore_files([ids[with_data[n]] for n in sel], source, [out_paths[n] for n in sel],
+                                    size_hints=[hints[n] for n in sel], window_bytes=window_bytes,
+                                    io_threads=io_threads)
+            return res, reused
+
+        def check(n: int, r):
+            k = with_data[n]
+            if r.bad_index is not None:
+                raise HbxError(f"block {ids[k][r.bad_index].hex()} (block {r.bad_index} of "
+                               f"{os.fsdecode(files[k][1])}) corrupted (status {r.bad_status})")
+            if r.errno:
+                raise HbxError(f"cannot write {os.fsdecode(files[k][1])}: {os.strerror(r.errno)}")
+            stats["bytes"] += r.bytes
+
+        try:
+            everything = list(range(len(with_data)))
+            res, reused = run(everything, True)
+            again = []
+            for n, r, u in zip(everything, res, reused):
+                if r.bad_index is not None and r.bad_index in u:
+                    again.append(n)  # the local file changed after it was hashed: a reuse is never trusted
+                    continue
+                check(n, r)
+                stats["blocks_reused"] += len(u)
+                stats["bytes_reused"] += sum(u.values())
+            if again:
+                stats["reuse_retried"] += len(again)
+                res, _ = run(again, False)  # once more, every block fetched
+                for n, r in zip(again, res):
+                    check(n, r)
+        finally:
+            for n in locked:
+                try:
+                    os.chmod(out_paths[n], files[with_data[n]][2])
+                except OSError:
+                    pass
+        for k in list(temps):
+            os.replace(temps[k], files[k][1])
+            del temps[k]
+    finally:
+        pool.close()
+        for tmp in temps.values():  # a failure: the old files stay as they were
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+
+
 def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_bytes: int = 0,
-                 batch: bool = False, io_threads: int = 16, keep_matching: bool = False) -> Dict[str, int]:
+                 batch: bool = False, io_threads: int = 16, keep_matching: bool = False,
+                 reuse_local: bool = False, reuse_paths: Sequence = ()) -> Dict[str, int]:
     """restoreEntry(root_entry, dest) (hashback/restore.go:68-162): the
     counterpart of :func:`store_tree`.  ``read_block(id)`` returns a block as
     it comes off the wire: ``(data type, data field, links)``.
@@ -484,6 +677,27 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
     ``bytes``.  Every other candidate is created or truncated and restored
     with the rest.
 
+    ``reuse_local=True`` (with ``batch=True``; a ValueError without it)
+    includes ``keep_matching`` and goes one step further, per block instead of
+    per file.  Every regular file already at an entry's path (of any size) and
+    every file in ``reuse_paths`` (a file's previous name, a copy elsewhere;
+    only read) is cut and hashed once; ``Engine.locate_ids`` (K13) then finds,
+    for each data block a file to restore needs, a local chunk with that ID,
+    and the block is read from that file instead of ``read_block``: a file
+    changed in one place, grown by a byte, renamed or copied fetches only the
+    blocks no local file holds.  A reused chunk enters the restore as a raw
+    block and is verified like a fetched one, so nothing rests on the local
+    files staying as they were hashed: a file whose first bad block was a
+    reused one is restored once more with every block fetched
+    (``stats["reuse_retried"]``); a bad fetched block raises as ever.  A file
+    that was there before is written to a temporary beside it and renamed over
+    it once every file of the call is good, so no local file is truncated
+    while it may still be read (two files that exchanged content restore
+    correctly), and after a failure the temporaries are gone and the old files
+    are as they were.  ``stats`` gains ``"kept"``, ``"blocks_reused"``,
+    ``"bytes_reused"``, ``"blocks_fetched"`` (data blocks read through
+    ``read_block``) and ``"reuse_retried"``; ``"bytes"`` stays the bytes written.
+
     Directory blocks and chain blocks are inflated and verified on the device
     with their links (``Engine.restore_blocks``), then parsed
     (``parse_directory_block`` / ``parse_chain_block``); regular files stream
@@ -496,9 +710,12 @@ def restore_tree(eng: Engine, root_entry: FileEntry, read_block, dest, window_by
     """
     if keep_matching and not batch:
         raise ValueError("keep_matching needs batch=True")
+    if reuse_local and not batch:
+        raise ValueError("reuse_local needs batch=True")
     dest = os.fsencode(os.fspath(dest))
     if batch:
-        return _restore_tree_batched(eng, root_entry, read_block, dest, window_bytes, io_threads, keep_matching)
+        return _restore_tree_batched(eng, root_entry, read_block, dest, window_bytes, io_threads, keep_matching,
+                                     reuse_local, reuse_paths)
     stats = {"files": 0, "directories": 0, "bytes": 0}
 
     def restore_entry(e: FileEntry, path: bytes):

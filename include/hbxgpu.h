@@ -967,6 +967,46 @@ int hbx_store_paths_match(hbx_ctx *ctx, uint64_t n_files, const char *const *pat
                           hbx_file_summary *summaries, int32_t *status, uint32_t io_threads, uint64_t batch_bytes,
                           const uint64_t *expect_first, const uint8_t *expect_ids, hbx_chain_match *match);
 
+/* ---- Restore over an existing tree: where local files hold wanted blocks (K13) -----
+ * restoreFileData (hashback/restore.go:45-66) fetches every block of every file
+ * it writes.  A block ID binds the block's length and bytes (block.go:96-111)
+ * and content-defined chunking leaves the IDs around a local change as they
+ * were, so a chunk of ANY local file that carries a wanted ID is that block:
+ * a file changed in one place, grown by a byte, renamed or copied needs only
+ * the blocks no local file holds.  K13 (hbx_k13_build, hbx_k13_lookup) is that
+ * join on the device: the pool's IDs go into a scratch slot table (K9's, with
+ * the pool index as payload), every wanted ID is looked up in it.  The caller
+ * reads the located bytes from the local file and hands them to VerifyBlock as
+ * a raw block (hbx_restore_files_stream): a local file that changed since it
+ * was hashed is found out there, never written. */
+typedef struct {
+  uint32_t file;     /* pool file holding the chunk; UINT32_MAX = not in the pool */
+  uint32_t chunk;    /* its index among that file's chunks */
+  uint64_t off;      /* where it starts in that file: the previous chunk's cut end, 0 for chunk 0 */
+  uint64_t len;      /* its length */
+  uint64_t reserved; /* 0 */
+} hbx_block_loc;     /* 32 bytes; on a miss chunk = 0, off = len = 0 */
+/* For each of n_want IDs (want_ids, 16 bytes each, host memory) the first place
+ * the pool holds it: pool file f's chunk IDs are pool_ids[16 pool_first[f] ..
+ * 16 pool_first[f + 1]) (pool_first: n_pool_files + 1 running counts, which need
+ * not start at 0), pool_cut_ends runs parallel to pool_ids with offsets
+ * relative to each file.  loc[j] names the LOWEST pool index whose 16 bytes
+ * equal want_ids[j], so the answer does not depend on the run; *n_found (may
+ * be NULL) is the number of hits.  Runs K13 alone on the result stream, as
+ * hbx_match_chains runs K12 alone.  Synchronous; HBX_ERR_STATE while batches
+ * are pending or after a failed submit; n_want == 0 is HBX_OK, nothing runs (*n_found = 0);
+ * an empty pool makes every record a miss.  HBX_ERR_ARG, before the context is
+ * touched: a NULL context; pool_first NULL with n_pool_files > 0; pool_ids or
+ * pool_cut_ends NULL while the pool holds an ID; want_ids or loc NULL with
+ * n_want > 0; running counts that decrease; more than 2^31 - 1 pool files, more
+ * than 2^30 pool IDs, more than 2^32 - 1 wanted IDs.
+ * Device memory, with np pool IDs, nw wanted IDs and S = hbx_idset_slots(np)
+ * table slots: 16 (np + nw) + 8 np + 8 (n_pool_files + 1) + 4 S + 32 nw bytes
+ * (+ 8 for the hit count), kept for the next call and freed by hbx_ctx_destroy. */
+int hbx_locate_ids(hbx_ctx *ctx, uint64_t n_pool_files, const uint64_t *pool_first,
+                   const uint8_t *pool_ids, const uint64_t *pool_cut_ends,
+                   uint64_t n_want, const uint8_t *want_ids, hbx_block_loc *loc, uint64_t *n_found);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
