@@ -44,6 +44,8 @@ EXPORTS = [
     "hbx_restore_many_window", "hbx_restore_files_blocks", "hbx_restore_files_stream",
     "hbx_match_chains", "hbx_submit_device_match", "hbx_store_paths_match",
     "hbx_k1_summaries", "hbx_locate_ids",
+    "hbx_datfile_header_parse", "hbx_datfile_entry_parse", "hbx_datfile_walk",
+    "hbx_datfile_check_device", "hbx_datfile_check_path", "hbx_datfile_verify_at",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -136,6 +138,43 @@ class BlockLoc(ctypes.Structure):
                 ("len", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
 
 
+class DatRecord(ctypes.Structure):
+    """hbx_dat_record: one position of a data file as K14's parse frames it."""
+    _fields_ = [("off", ctypes.c_uint64), ("size", ctypes.c_uint64), ("data_off", ctypes.c_uint64),
+                ("links_off", ctypes.c_uint64), ("data_len", ctypes.c_uint32), ("n_links", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("type", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("pad", ctypes.c_uint16), ("id", ctypes.c_uint8 * 16)]
+
+
+class DatEntry(ctypes.Structure):
+    """hbx_dat_entry: a good entry on the walk of a data file."""
+    _fields_ = [("off", ctypes.c_uint64), ("size", ctypes.c_uint64), ("data_off", ctypes.c_uint64),
+                ("link_base", ctypes.c_uint64), ("n_links", ctypes.c_uint32), ("data_len", ctypes.c_uint32),
+                ("plain_len", ctypes.c_uint32), ("type", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3),
+                ("id", ctypes.c_uint8 * 16)]
+
+
+class DatSpan(ctypes.Structure):
+    """hbx_dat_span: a gap or a broken span of a data file."""
+    _fields_ = [("off", ctypes.c_uint64), ("len", ctypes.c_uint64), ("kind", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("n_failed", ctypes.c_uint64)]
+
+
+class DatSummary(ctypes.Structure):
+    """hbx_dat_summary: what a check of a data file found."""
+    _fields_ = [("size", ctypes.c_uint64), ("filetype", ctypes.c_uint32), ("version", ctypes.c_uint32),
+                ("deadspace", ctypes.c_uint64), ("header_ok", ctypes.c_uint32), ("gap_past_eof", ctypes.c_uint32),
+                ("n_candidates", ctypes.c_uint64), ("n_gap_markers", ctypes.c_uint64), ("n_valid", ctypes.c_uint64),
+                ("n_unreached", ctypes.c_uint64), ("n_entries", ctypes.c_uint64), ("entry_bytes", ctypes.c_uint64),
+                ("n_gaps", ctypes.c_uint64), ("gap_bytes", ctypes.c_uint64), ("n_broken", ctypes.c_uint64),
+                ("broken_bytes", ctypes.c_uint64), ("n_spans", ctypes.c_uint64), ("n_links", ctypes.c_uint64),
+                ("truncate_at", ctypes.c_uint64)]
+
+
+DAT_HEADER, DAT_IMAGE_SLACK = 16, 64            # HBX_DAT_HEADER, HBX_DAT_IMAGE_SLACK
+DAT_ST_INVALID, DAT_ST_WRONG_ID = 9, 10         # HBX_DAT_ST_*
+DAT_F_MARKER, DAT_F_GAP = 1, 2                  # HBX_DAT_F_*
+DAT_SPAN_GAP, DAT_SPAN_BROKEN = 0, 1            # HBX_DAT_SPAN_*
 NO_FILE = 0xFFFFFFFF                # hbx_block_loc.file of an ID the pool does not hold
 BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
 MAX_BLOCK = 8 << 20                 # HBX_MAX_BLOCK
@@ -276,6 +315,14 @@ def load() -> ctypes.CDLL:
     L.hbx_submit_device_match.argtypes = L.hbx_submit_device.argtypes + [P, P, P]
     L.hbx_store_paths_match.argtypes = [P, U64, P, P, P, P, P, P, P, P, ctypes.c_uint32, U64, P, P, P]
     L.hbx_locate_ids.argtypes = [P, U64, P, P, P, U64, P, P, PU64]
+    L.hbx_datfile_header_parse.argtypes = [P, U64, PU32, PU32, PU64]
+    L.hbx_datfile_entry_parse.argtypes = [P, U64, U64, U64, ctypes.POINTER(DatRecord)]
+    L.hbx_datfile_walk.argtypes = [U64, U64, P, P, U64, P, P, P, U64, P, U64, ctypes.POINTER(DatSummary)]
+    L.hbx_datfile_check_device.argtypes = [P, P, U64, U64, U64, U64, P, U64, P, U64, P, U64,
+                                           ctypes.POINTER(DatSummary)]
+    L.hbx_datfile_check_path.argtypes = [P, ctypes.c_char_p, U64, U64, U64, P, U64, P, U64, P, U64,
+                                         ctypes.POINTER(DatSummary)]
+    L.hbx_datfile_verify_at.argtypes = [P, P, U64, ctypes.c_char_p, U64, P, P, I, U64, U64, P]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

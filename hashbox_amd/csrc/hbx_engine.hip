@@ -45,8 +45,10 @@
 #include "hbx_locate.hip"
 #include "hbx_restore.hip"
 #include "hbx_restore_many.hip"
+#include "hbx_datfile.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
+#include "hbx_datfile.h"
 
 namespace {
 
@@ -451,6 +453,13 @@ struct hbx_ctx {
   DevBuf d_mt[5], d_mtout;        // hbx_match_chains: the two ID lists, their firsts, the cut ends; the records
   // hbx_locate_ids: the pool's IDs, cut ends and firsts, the wanted IDs, the slot table, the records + hit count
   DevBuf d_lc[6];
+  // hbx_datfile_*: K14's two position lists + counts, the sorted positions, the records; the image and the
+  // two pinned staging buffers of the path variants; K14's workgroup count (0 = by size; HBX_K14_WGS: tests);
+  // the latest call's windows and streams inflated again
+  DevBuf d_df[3], d_dfimg;
+  PinBuf h_dfstage[2];
+  uint32_t k14_wgs = 0;
+  uint64_t dat_windows = 0, dat_retries = 0;
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -1889,6 +1898,8 @@ int hbx_ctx_create(int device, hbx_ctx** out) {
   if (const char* v = ab_env("HBX_K3_ITEMS")) c->k3_items = (uint32_t)std::min(8, std::max(0, std::atoi(v)));
   // (tests: a K3 grid of a few workgroups, so every wave takes many groups)
   if (const char* v = ab_env("HBX_K3_WGS")) c->md5_wgs = (uint32_t)std::min<int>(std::max(1, ncu), std::max(1, std::atoi(v)));
+  // (tests: a K14 grid of one or two workgroups, so a small image spans several grid-stride rounds)
+  if (const char* v = ab_env("HBX_K14_WGS")) c->k14_wgs = (uint32_t)std::min(65536, std::max(0, std::atoi(v)));
   if (hipSetDevice(device) != hipSuccess || make_stream(&c->stream, "HBX_SCAN_CUS", ncu, "0:4096") != hipSuccess) {
     delete c;
     return HBX_ERR_HIP;
@@ -1966,6 +1977,9 @@ void hbx_ctx_destroy(hbx_ctx* c) {
   for (DevBuf& d : c->d_mt) d.release();
   c->d_mtout.release();
   for (DevBuf& d : c->d_lc) d.release();
+  for (DevBuf& d : c->d_df) d.release();
+  c->d_dfimg.release();
+  for (PinBuf& h : c->h_dfstage) h.release();
   for (hbx_seg* h : c->segs_open) delete h;
   for (DevBuf& d : c->seg_words) d.release();
   c->d_segmsg.release();
@@ -2143,7 +2157,7 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"k8_split_fallbacks\": %llu, \"gate_meta\": %u, \"sdma_warm\": %u, \"sdma_h2d_mask\": %u, "
       "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
       "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu], "
-      "\"match_push_bytes\": %llu}",
+      "\"match_push_bytes\": %llu, \"k14_wgs\": %u, \"datfile\": [%llu, %llu]}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
@@ -2151,7 +2165,8 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       c->sdma_warm, c->sdma_h2d, c->sdma_d2h, c->sdma_warm_ms, c->k3_spin, c->plan_addr, c->plan_addr_shift, c->k1_ext, c->k1_dma4, c->k1_early,
       c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3],
       (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries,
-      (unsigned long long)c->match_push_bytes);
+      (unsigned long long)c->match_push_bytes, c->k14_wgs, (unsigned long long)c->dat_windows,
+      (unsigned long long)c->dat_retries);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -2806,19 +2821,22 @@ namespace {
 // are about equally long.  The restore path passes arena = NULL with absolute
 // device addresses in offs (its blocks lie in two buffers): the sum is only
 // ever turned into an integer address, so that is part of this contract.
+// link_addr (the data file path, whose links lie in the device image beside
+// the data): block i's links are at that device address and `links` /
+// `link_base` are not used.
 int verify_device(hbx_ctx* c, const uint8_t* arena, uint64_t n, const uint64_t* offs,
                   const uint64_t* lens, const uint8_t* links, const uint64_t* link_base,
                   const uint32_t* n_links, uint8_t* ids, const uint8_t* expect, uint8_t* ok,
-                  uint64_t* n_bad) {
+                  uint64_t* n_bad, const uint64_t* link_addr = nullptr) {
   if (n_bad) *n_bad = 0;
   if (n == 0) return HBX_OK;
   if (n > 0xFFFFFFFFull) return c->fail(HBX_ERR_ARG, "too many blocks");
   uint64_t nlinks_total = 0;
   for (uint64_t i = 0; i < n; i++) {
     const uint32_t nl = n_links ? n_links[i] : 0u;
-    if (nl && (!links || !link_base)) return c->fail(HBX_ERR_ARG, "links missing");
+    if (nl && !link_addr && (!links || !link_base)) return c->fail(HBX_ERR_ARG, "links missing");
     if (lens[i] + 8ull + 16ull * nl + 128ull > 0xFFFFFFFFull) return c->fail(HBX_ERR_ARG, "block too large");
-    if (nl) nlinks_total = std::max(nlinks_total, link_base[i] + nl);
+    if (nl && !link_addr) nlinks_total = std::max(nlinks_total, link_base[i] + nl);
   }
   std::vector<uint32_t> perm(n);
   for (uint64_t i = 0; i < n; i++) perm[i] = (uint32_t)i;
@@ -2835,7 +2853,7 @@ int verify_device(hbx_ctx* c, const uint8_t* arena, uint64_t n, const uint64_t* 
     const uint32_t i = perm[k];
     const uint32_t nl = n_links ? n_links[i] : 0u;
     desc[k].src = reinterpret_cast<uint64_t>(arena) + offs[i];
-    desc[k].links = reinterpret_cast<uint64_t>(dl + (nl ? 16 * link_base[i] : 0));
+    desc[k].links = link_addr ? link_addr[i] : reinterpret_cast<uint64_t>(dl + (nl ? 16 * link_base[i] : 0));
     desc[k].len = (uint32_t)lens[i];
     desc[k].n_links = nl;
     desc[k].pad = 0;
@@ -5809,6 +5827,427 @@ int hbx_restore_files_stream(hbx_ctx* c, uint64_t n_files, const uint64_t* first
                      : local_len[f] != R.run[f]  ? std::min(local_len[f], R.run[f])
                                                  : hbxr::kNoDiff;
   }
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- storage data files (hbx_datfile.hip, K14; hbx_datfile.h) ----------------------
+namespace {
+
+constexpr uint64_t kDatCandidates = 1ull << 20;  // max_candidates = 0
+constexpr uint64_t kDatStage = 32ull << 20;      // one pinned staging buffer of the path variants
+
+// The slot a zlib entry gets before its inflated size is known (as restore_window's estimate).
+inline uint64_t dat_share(uint64_t mb, uint64_t len) { return std::min<uint64_t>(mb, 8 * len + 4096); }
+
+// K14's parse over n positions (host memory; the first n_entries are entry
+// positions, the rest gap markers): the records come back in the same order.
+int datfile_frame(hbx_ctx* c, const uint8_t* image, uint64_t size, uint64_t mb, const uint64_t* pos, uint64_t n,
+                  uint64_t n_entries, std::vector<hbx_dat_record>& rec) {
+  rec.resize(n);
+  if (n == 0) return HBX_OK;
+  if (n > 0x7FFFFFFFull * hbxf::kThreads) return c->fail(HBX_ERR_ARG, "data file: too many positions");
+  hipStream_t s = c->stream;
+  HBX_TRY(c, c->d_df[1].ensure(n * 8));
+  HBX_TRY(c, c->d_df[2].ensure(n * sizeof(hbx_dat_record)));
+  HBX_TRY(c, hipMemcpyAsync(c->d_df[1].p, pos, n * 8, hipMemcpyHostToDevice, s));
+  const hbxf::ParseArgs pa{image, size, c->d_df[1].as<uint64_t>(), c->d_df[2].as<uint4>(), n, n_entries,
+                           hbx_restore_in_bound(mb)};
+  hipLaunchKernelGGL(hbx_k14_parse, dim3((uint32_t)((n + hbxf::kThreads - 1) / hbxf::kThreads)), dim3(hbxf::kThreads),
+                     0, s, pa);
+  HBX_TRY(c, hipGetLastError());
+  HBX_TRY(c, hipMemcpyAsync(rec.data(), c->d_df[2].p, n * sizeof(hbx_dat_record), hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipStreamSynchronize(s));
+  return HBX_OK;
+}
+
+// Inflate (K8 / K8s) and VerifyBlock (K6, links read from the image) every
+// record with status 0 that frames an entry, in place, in windows whose slots
+// fit wb by hbx_restore_many_window's rule.  A zlib entry's slot is its
+// share (dat_share); a stream that outgrows it is inflated again into a
+// max_block slot, as hbx_restore_files_* treats a size hint.  rec[i].status
+// becomes the entry's status (0..8), plain[i] its inflated length.
+int datfile_verify(hbx_ctx* c, const uint8_t* image, uint64_t mb, uint64_t wb, std::vector<hbx_dat_record>& rec,
+                   std::vector<uint32_t>& plain) {
+  plain.assign(rec.size(), 0u);
+  std::vector<uint64_t> v, caps;
+  for (uint64_t i = 0; i < rec.size(); i++)
+    if (!(rec[i].flags & HBX_DAT_F_GAP) && rec[i].status == 0) {
+      // (K6 frames a message in 32 bits: links and data beyond that are not accepted)
+      if (16ull * rec[i].n_links + rec[i].data_len + 136ull > 0xFFFFFFFFull) {
+        rec[i].status = 8;
+        continue;
+      }
+      v.push_back(i);
+      caps.push_back(rec[i].type == HBX_BLOCK_ZLIB ? dat_share(mb, rec[i].data_len) : 0);
+    }
+  if (v.empty()) return HBX_OK;
+  HBX_TRY(c, c->d_rword.ensure(4096));
+  const uint64_t base = reinterpret_cast<uint64_t>(image), stride = restore_stride(mb);
+  std::vector<uint64_t> addr, dlen, laddr;
+  std::vector<uint32_t> st, nl;
+  std::vector<uint8_t> expect, ok;
+  // VerifyBlock of the window's blocks js (indices into v) at addr / dlen
+  auto verify = [&](const std::vector<uint64_t>& js, uint64_t s0) -> int {
+    const uint64_t m = js.size();
+    if (m == 0) return HBX_OK;
+    std::vector<uint64_t> a(m), l(m);
+    laddr.resize(m);
+    nl.resize(m);
+    expect.resize(16 * m);
+    ok.assign(m, 0);
+    for (uint64_t q = 0; q < m; q++) {
+      const hbx_dat_record& r = rec[v[js[q]]];
+      a[q] = addr[js[q] - s0];
+      l[q] = dlen[js[q] - s0];
+      laddr[q] = base + r.links_off;
+      nl[q] = r.n_links;
+      std::memcpy(&expect[16 * q], r.id, 16);
+    }
+    if (int rc = verify_device(c, nullptr, m, a.data(), l.data(), nullptr, nullptr, nl.data(), nullptr,
+                               expect.data(), ok.data(), nullptr, laddr.data()))
+      return rc;
+    for (uint64_t q = 0; q < m; q++)
+      if (!ok[q]) st[js[q] - s0] = 7;
+    return HBX_OK;
+  };
+  for (uint64_t s = 0; s < v.size();) {
+    const uint64_t e = many_window_end(v.size(), caps.data(), wb, s), n = e - s;
+    c->dat_windows++;
+    std::vector<uint64_t> zi, in_offs, in_lens, out_offs, out_caps, out_lens, again, first;
+    std::vector<uint32_t> zst;
+    uint64_t slots = 0;
+    addr.assign(n, reinterpret_cast<uint64_t>(c->d_rword.p));
+    dlen.assign(n, 0);
+    st.assign(n, 0u);
+    for (uint64_t j = s; j < e; j++) {
+      const hbx_dat_record& r = rec[v[j]];
+      if (r.type == HBX_BLOCK_ZLIB) {
+        zi.push_back(j);
+        in_offs.push_back(base + r.data_off);
+        in_lens.push_back(r.data_len);
+        out_offs.push_back(slots);
+        out_caps.push_back(caps[j]);
+        slots += many_slot(caps[j]);
+      } else if (r.data_len > mb) {
+        st[j - s] = hbxi::kErrOutput;
+      } else {
+        addr[j - s] = base + r.data_off;
+        dlen[j - s] = r.data_len;
+      }
+    }
+    const uint64_t nz = zi.size();
+    out_lens.assign(nz, 0);
+    zst.assign(nz, 0u);
+    if (nz) {
+      HBX_TRY(c, c->d_rslots.ensure(slots + 65536));
+      if (int rc = inflate_device(c, nullptr, nz, in_offs.data(), in_lens.data(), c->d_rslots.p, out_offs.data(),
+                                  out_caps.data(), out_lens.data(), zst.data()))
+        return rc;
+    }
+    for (uint64_t k = 0; k < nz; k++) {
+      const uint64_t j = zi[k];
+      st[j - s] = zst[k];
+      if (zst[k] == 0) {
+        addr[j - s] = reinterpret_cast<uint64_t>(c->d_rslots.p) + out_offs[k];
+        dlen[j - s] = out_lens[k];
+      } else if (zst[k] == hbxi::kErrOutput && caps[j] < mb) {
+        again.push_back(j);
+      }
+    }
+    for (uint64_t j = s; j < e; j++)
+      if (st[j - s] == 0) first.push_back(j);
+    if (int rc = verify(first, s)) return rc;
+    // the streams that outgrew their share, as many at a time as max_block slots fit the window
+    const uint64_t per = std::max<uint64_t>(1, wb / stride);
+    for (uint64_t g = 0; g < again.size(); g += per) {
+      const uint64_t m = std::min<uint64_t>(per, again.size() - g);
+      c->dat_retries += m;
+      std::vector<uint64_t> r_in(m), r_len(m), r_out(m), r_cap(m, mb), r_hint(m), r_olen(m, 0), js;
+      std::vector<uint32_t> rst(m, 0u);
+      for (uint64_t q = 0; q < m; q++) {
+        const hbx_dat_record& r = rec[v[again[g + q]]];
+        r_in[q] = base + r.data_off;
+        r_len[q] = r.data_len;
+        r_out[q] = q * stride;
+        r_hint[q] = dat_share(mb, r.data_len);
+      }
+      HBX_TRY(c, c->d_rretry.ensure(m * stride + 65536));
+      if (int rc = inflate_device(c, nullptr, m, r_in.data(), r_len.data(), c->d_rretry.p, r_out.data(), r_cap.data(),
+                                  r_olen.data(), rst.data(), r_hint.data()))
+        return rc;
+      for (uint64_t q = 0; q < m; q++) {
+        const uint64_t j = again[g + q];
+        st[j - s] = rst[q];
+        if (rst[q] == 0) {
+          addr[j - s] = reinterpret_cast<uint64_t>(c->d_rretry.p) + r_out[q];
+          dlen[j - s] = r_olen[q];
+          js.push_back(j);
+        }
+      }
+      if (int rc = verify(js, s)) return rc;
+    }
+    for (uint64_t j = s; j < e; j++) {
+      rec[v[j]].status = st[j - s];
+      plain[v[j]] = (uint32_t)dlen[j - s];
+    }
+    s = e;
+  }
+  return HBX_OK;
+}
+
+// The file at `path` into the context's image buffer through the two pinned
+// staging buffers: chunk k is read while chunk k - 1 is copied.
+int datfile_load(hbx_ctx* c, const char* path, const uint8_t** image, uint64_t* size) {
+  const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+  if (fd < 0) return c->fail(HBX_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+  hipEvent_t done[2] = {nullptr, nullptr};
+  const int rc = [&]() -> int {
+    const off_t end = ::lseek(fd, 0, SEEK_END);
+    if (end < 0) return c->fail(HBX_ERR_IO, std::string("cannot size ") + path + ": " + std::strerror(errno));
+    const uint64_t n = (uint64_t)end, need = n + 65536;
+    if (need > c->d_dfimg.cap) {
+      size_t fr = 0, tot = 0;
+      HBX_TRY(c, hipMemGetInfo(&fr, &tot));
+      if (need > (fr + c->d_dfimg.cap) / 3)
+        return c->fail(HBX_ERR_CAPACITY, std::string(path) + " does not fit a third of the free device memory");
+    }
+    HBX_TRY(c, c->d_dfimg.ensure(need));
+    uint8_t* img = c->d_dfimg.as<uint8_t>();
+    hipStream_t s = c->stream;
+    HBX_TRY(c, hipMemsetAsync(img + n, 0, 4096, s));
+    for (int b = 0; b < 2 && (uint64_t)b * kDatStage < n; b++) {
+      HBX_TRY(c, c->h_dfstage[b].ensure(std::min(kDatStage, n)));
+      HBX_TRY(c, hipEventCreateWithFlags(&done[b], hipEventDisableTiming));
+    }
+    std::string err;
+    for (uint64_t at = 0, k = 0; at < n; at += kDatStage, k++) {
+      const uint64_t len = std::min(kDatStage, n - at);
+      const int b = (int)(k & 1);
+      if (k >= 2) HBX_TRY(c, hipEventSynchronize(done[b]));
+      if (read_range(fd, path, at, len, c->h_dfstage[b].as<uint8_t>(), 8, err)) return c->fail(HBX_ERR_IO, err);
+      HBX_TRY(c, hipMemcpyAsync(img + at, c->h_dfstage[b].p, len, hipMemcpyHostToDevice, s));
+      HBX_TRY(c, hipEventRecord(done[b], s));
+    }
+    HBX_TRY(c, hipStreamSynchronize(s));
+    *image = img;
+    *size = n;
+    return HBX_OK;
+  }();
+  if (rc) (void)hipStreamSynchronize(c->stream);  // (a copy may still read a staging buffer)
+  for (hipEvent_t e : done)
+    if (e) (void)hipEventDestroy(e);
+  ::close(fd);
+  return rc;
+}
+
+int datfile_check(hbx_ctx* c, const uint8_t* image, uint64_t size, uint64_t mb, uint64_t max_candidates, uint64_t wb,
+                  hbx_dat_entry* entries, uint64_t entry_cap, hbx_dat_span* spans, uint64_t span_cap, uint8_t* links,
+                  uint64_t link_cap, hbx_dat_summary* sum) {
+  std::memset(sum, 0, sizeof *sum);
+  sum->size = size;
+  sum->truncate_at = ~0ull;
+  c->dat_windows = c->dat_retries = 0;
+  hipStream_t s = c->stream;
+  uint8_t hdr[HBX_DAT_HEADER] = {0};
+  const uint64_t hn = std::min<uint64_t>(size, HBX_DAT_HEADER);
+  if (hn) {
+    HBX_TRY(c, hipMemcpyAsync(hdr, image, hn, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+  }
+  sum->header_ok = hbxdat::header_parse(hdr, hn, &sum->filetype, &sum->version, &sum->deadspace) == HBX_OK ? 1u : 0u;
+  // 1. K14 scan: every "hblk" and "Cgap" at a position in [16, size - 4]
+  const uint64_t cap = std::min<uint64_t>(max_candidates ? max_candidates : kDatCandidates, std::max<uint64_t>(size, 1));
+  unsigned long long counts[2] = {0, 0};
+  std::vector<uint64_t> pos;
+  if (size >= HBX_DAT_HEADER + 4) {
+    HBX_TRY(c, c->d_df[0].ensure(2 * cap * 8 + 16));
+    uint64_t* lists = c->d_df[0].as<uint64_t>();
+    unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(lists + 2 * cap);
+    HBX_TRY(c, hipMemsetAsync(d_counts, 0, 16, s));
+    const hbxf::ScanArgs sa{image, size, lists, lists + cap, d_counts, cap};
+    hipLaunchKernelGGL(hbx_k14_scan, dim3(hbxf::scan_grid(size, c->k14_wgs)), dim3(hbxf::kThreads), 0, s, sa);
+    HBX_TRY(c, hipGetLastError());
+    HBX_TRY(c, hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    sum->n_candidates = counts[0];
+    sum->n_gap_markers = counts[1];
+    if (counts[0] > cap || counts[1] > cap)
+      return c->fail(HBX_ERR_CAPACITY, "data file: " + std::to_string(counts[0]) + " entry markers and " +
+                                           std::to_string(counts[1]) + " gap markers, max_candidates is " +
+                                           std::to_string(cap));
+    pos.resize(counts[0] + counts[1]);
+    if (counts[0]) HBX_TRY(c, hipMemcpyAsync(pos.data(), lists, counts[0] * 8, hipMemcpyDeviceToHost, s));
+    if (counts[1])
+      HBX_TRY(c, hipMemcpyAsync(pos.data() + counts[0], lists + cap, counts[1] * 8, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    // the lists come in the order the waves' adds landed: sorted, the result is the same on every run
+    std::sort(pos.begin(), pos.begin() + counts[0]);
+    std::sort(pos.begin() + counts[0], pos.end());
+  }
+  // 2. K14 parse: a record per position
+  std::vector<hbx_dat_record> rec;
+  if (int rc = datfile_frame(c, image, size, mb, pos.data(), pos.size(), counts[0], rec)) return rc;
+  std::vector<uint64_t> gap_offs;
+  std::vector<int64_t> gap_skips;
+  for (uint64_t i = counts[0]; i < rec.size(); i++)
+    if (rec[i].status == 0) {
+      gap_offs.push_back(rec[i].off);
+      gap_skips.push_back((int64_t)rec[i].size);
+    }
+  rec.resize(counts[0]);
+  for (const hbx_dat_record& r : rec) sum->n_valid += r.status == 0 ? 1 : 0;
+  // 3. every structurally valid candidate inflated and verified in place
+  std::vector<uint32_t> plain;
+  if (int rc = datfile_verify(c, image, mb, wb, rec, plain)) return rc;
+  // 4. the walk
+  int rc = hbxdat::walk(size, rec.size(), rec.data(), plain.data(), gap_offs.size(), gap_offs.data(), gap_skips.data(),
+                        entries, entry_cap, spans, span_cap, sum);
+  sum->n_gap_markers = counts[1];  // (the walk saw only those with 12 bytes inside the file)
+  if (rc) c->fail(rc, "data file: " + std::to_string(sum->n_entries) + " entries and " + std::to_string(sum->n_spans) +
+                          " spans do not fit the output capacities");
+  // 5. the good entries' links, flat: K11's gather out of the image, one copy back
+  if (rc == HBX_OK && links && sum->n_links > link_cap)
+    rc = c->fail(HBX_ERR_CAPACITY, "data file: " + std::to_string(sum->n_links) + " links, link_cap is " +
+                                       std::to_string(link_cap));
+  if (rc == HBX_OK && links && sum->n_links) {
+    std::vector<hbxm::Piece> pieces;
+    for (uint64_t i = 0; i < sum->n_entries; i++) {
+      const hbx_dat_entry& e = entries[i];
+      const uint64_t len = 16ull * e.n_links, src = reinterpret_cast<uint64_t>(image) + e.off + 24;
+      for (uint64_t p = 0; p < len; p += hbxm::kPieceMany)
+        pieces.push_back(hbxm::Piece{src + p, 16 * e.link_base + p, p,
+                                     (uint32_t)std::min<uint64_t>(hbxm::kPieceMany, len - p), 0u});
+    }
+    if (pieces.size() > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "data file: too many links");
+    HBX_TRY(c, c->d_rpiece.ensure(pieces.size() * sizeof(hbxm::Piece)));
+    HBX_TRY(c, c->d_rimg.ensure(16 * sum->n_links + 256));
+    HBX_TRY(c, hipMemcpyAsync(c->d_rpiece.p, pieces.data(), pieces.size() * sizeof(hbxm::Piece), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(hbx_k11_gather, dim3((uint32_t)((pieces.size() + hbxm::kWaves - 1) / hbxm::kWaves)),
+                       dim3(hbxm::kThreads), 0, s, c->d_rpiece.as<hbxm::Piece>(), (uint32_t)pieces.size(),
+                       c->d_rimg.as<uint8_t>());
+    HBX_TRY(c, hipGetLastError());
+    HBX_TRY(c, hipMemcpyAsync(links, c->d_rimg.p, 16 * sum->n_links, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+  }
+  return rc;
+}
+
+int datfile_verify_at(hbx_ctx* c, const uint8_t* image, uint64_t size, uint64_t n, const uint64_t* offs,
+                      const uint8_t* expect_ids, int content, uint64_t mb, uint64_t wb, uint32_t* status) {
+  c->dat_windows = c->dat_retries = 0;
+  std::vector<hbx_dat_record> rec;
+  if (int rc = datfile_frame(c, image, size, mb, offs, n, n, rec)) return rc;
+  for (uint64_t i = 0; i < n; i++)
+    if (rec[i].status == 0 && std::memcmp(rec[i].id, expect_ids + 16 * i, 16) != 0) rec[i].status = HBX_DAT_ST_WRONG_ID;
+  if (content) {
+    std::vector<uint32_t> plain;
+    if (int rc = datfile_verify(c, image, mb, wb, rec, plain)) return rc;
+  }
+  for (uint64_t i = 0; i < n; i++) status[i] = rec[i].status;
+  return HBX_OK;
+}
+
+// window_bytes = 0: an eighth of the free device memory, at least 1 GiB and at most 32 GiB.  Every window
+// costs the serial time of its longest stream and its longest block (one wave, one lane), so few large windows
+// are faster than many small ones; the retry slots may take as much again and the split scratch a quarter.
+inline uint64_t dat_window(uint64_t wb) {
+  if (wb) return wb;
+  size_t fr = 0, tot = 0;
+  uint64_t b = kManyWindow;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess) b = std::max<uint64_t>(b, std::min<uint64_t>(fr / 8, 32ull << 30));
+  return b;
+}
+
+// Argument checks shared by the three calls (before the context is touched).
+inline bool datfile_args_ok(const void* d_image, uint64_t max_block) {
+  return (reinterpret_cast<uintptr_t>(d_image) & (HBX_ARENA_ALIGN - 1)) == 0 && restore_mb(max_block) <= kRestoreMaxBlock;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hbx_datfile_header_parse(const uint8_t* in, uint64_t len, uint32_t* filetype, uint32_t* version,
+                             uint64_t* deadspace) {
+  if (!in && len) return HBX_ERR_ARG;
+  return hbxdat::header_parse(in, len, filetype, version, deadspace);
+}
+
+int hbx_datfile_entry_parse(const uint8_t* image, uint64_t size, uint64_t off, uint64_t max_block,
+                            hbx_dat_record* rec) {
+  if (!rec || (!image && size) || restore_mb(max_block) > kRestoreMaxBlock) return HBX_ERR_ARG;
+  hbxdat::entry_parse(image, size, off, hbx_restore_in_bound(max_block), rec);
+  return HBX_OK;
+}
+
+int hbx_datfile_walk(uint64_t size, uint64_t n_cand, const hbx_dat_record* cand, const uint32_t* plain_len,
+                     uint64_t n_gaps, const uint64_t* gap_offs, const int64_t* gap_skips, hbx_dat_entry* entries,
+                     uint64_t entry_cap, hbx_dat_span* spans, uint64_t span_cap, hbx_dat_summary* summary) {
+  if (!summary || (n_cand && !cand) || (n_gaps && (!gap_offs || !gap_skips)) || (entry_cap && !entries) ||
+      (span_cap && !spans))
+    return HBX_ERR_ARG;
+  for (uint64_t i = 1; i < n_cand; i++)
+    if (cand[i].off <= cand[i - 1].off) return HBX_ERR_ARG;
+  for (uint64_t i = 1; i < n_gaps; i++)
+    if (gap_offs[i] <= gap_offs[i - 1]) return HBX_ERR_ARG;
+  return hbxdat::walk(size, n_cand, cand, plain_len, n_gaps, gap_offs, gap_skips, entries, entry_cap, spans, span_cap,
+                      summary);
+}
+
+int hbx_datfile_check_device(hbx_ctx* c, const void* d_image, uint64_t size, uint64_t max_block,
+                             uint64_t max_candidates, uint64_t window_bytes, hbx_dat_entry* entries,
+                             uint64_t entry_cap, hbx_dat_span* spans, uint64_t span_cap, uint8_t* links,
+                             uint64_t link_cap, hbx_dat_summary* summary) {
+  if (!c || !d_image || !summary || (entry_cap && !entries) || (span_cap && !spans) || (link_cap && !links) ||
+      !datfile_args_ok(d_image, max_block))
+    return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  const int rc = datfile_check(c, static_cast<const uint8_t*>(d_image), size, restore_mb(max_block), max_candidates,
+                               dat_window(window_bytes), entries, entry_cap, spans, span_cap, links,
+                               link_cap, summary);
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int hbx_datfile_check_path(hbx_ctx* c, const char* path, uint64_t max_block, uint64_t max_candidates,
+                           uint64_t window_bytes, hbx_dat_entry* entries, uint64_t entry_cap, hbx_dat_span* spans,
+                           uint64_t span_cap, uint8_t* links, uint64_t link_cap, hbx_dat_summary* summary) {
+  if (!c || !path || !summary || (entry_cap && !entries) || (span_cap && !spans) || (link_cap && !links) ||
+      !datfile_args_ok(nullptr, max_block))
+    return HBX_ERR_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  const uint8_t* image = nullptr;
+  uint64_t size = 0;
+  int rc = datfile_load(c, path, &image, &size);
+  if (rc == HBX_OK)
+    rc = datfile_check(c, image, size, restore_mb(max_block), max_candidates, dat_window(window_bytes),
+                       entries, entry_cap, spans, span_cap, links, link_cap, summary);
+  if (rc) (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+
+int hbx_datfile_verify_at(hbx_ctx* c, const void* d_image, uint64_t size, const char* path, uint64_t n,
+                          const uint64_t* offs, const uint8_t* expect_ids, int content, uint64_t max_block,
+                          uint64_t window_bytes, uint32_t* status) {
+  if (!c || (d_image != nullptr) == (path != nullptr) || (n && (!offs || !expect_ids || !status)) ||
+      !datfile_args_ok(d_image, max_block))
+    return HBX_ERR_ARG;
+  if (n == 0) return HBX_OK;
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  HBX_TRY(c, hipSetDevice(c->device));
+  const uint8_t* image = static_cast<const uint8_t*>(d_image);
+  int rc = path ? datfile_load(c, path, &image, &size) : HBX_OK;
+  if (rc == HBX_OK)
+    rc = datfile_verify_at(c, image, size, n, offs, expect_ids, content, restore_mb(max_block),
+                           dat_window(window_bytes), status);
+  if (rc) (void)hipStreamSynchronize(c->stream);
   return rc;
 }
 

@@ -89,6 +89,24 @@ class RestoredFile:
     first_diff: Optional[int] = None  # diff mode
 
 
+DAT_ENTRY_DTYPE = np.dtype([("off", np.uint64), ("size", np.uint64), ("data_off", np.uint64), ("link_base", np.uint64),
+                            ("n_links", np.uint32), ("data_len", np.uint32), ("plain_len", np.uint32),
+                            ("type", np.uint8), ("id", np.uint8, (16,))])
+DAT_SPAN_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint64), ("kind", np.uint32), ("status", np.uint32),
+                           ("n_failed", np.uint64)])
+
+
+@dataclass(slots=True)
+class DatFileCheck:
+    """What :meth:`Engine.check_datfile` returns (hbx_datfile_check_*): what
+    RecoverData (pkg/storagedb/integrity.go:74-143) would find in a storage
+    data file."""
+    entries: np.ndarray  # DAT_ENTRY_DTYPE [n_entries]: the good entries on the walk, ascending
+    spans: np.ndarray  # DAT_SPAN_DTYPE [n_spans]: gaps (kind 0) and broken spans (kind 1), ascending
+    summary: dict  # hbx_dat_summary's fields; truncate_at is None when the walk did not end in damage
+    links: Optional[np.ndarray]  # uint8 [summary["n_links"], 16]: entry e's are links[link_base : link_base + n_links]
+
+
 def max_chunks(n: int) -> int:
     return n // MIN_BLOCK_SIZE + 1
 
@@ -579,6 +597,109 @@ class Engine:
         for name in out.dtype.names:
             out[name] = v[name]
         return out
+
+    def _dat_image(self, source, size):
+        """(device pointer, size, path, arena to free) of a data file given as
+        a path, as bytes or as a device pointer with its size."""
+        if isinstance(source, (str, os.PathLike)):
+            return None, 0, os.fsencode(source), None
+        if isinstance(source, int):
+            if size is None:
+                raise ValueError("a device pointer needs size=")
+            self._after_producer()
+            return ctypes.c_void_p(source), int(size), None, None
+        a = _u8(source)
+        n = int(a.shape[0])
+        padded = np.zeros(n + _lib.DAT_IMAGE_SLACK, np.uint8)
+        padded[:n] = a
+        d = ctypes.c_void_p()
+        self._check(self._L.hbx_arena_alloc(self._ctx, padded.shape[0], ctypes.byref(d)), "hbx_arena_alloc")
+        rc = self._L.hbx_memcpy_h2d(self._ctx, d, _p(padded), padded.shape[0])
+        if rc != 0:
+            self._L.hbx_arena_free(self._ctx, d)
+            self._check(rc, "hbx_memcpy_h2d")
+        return d, n, None, d
+
+    def check_datfile(self, source, max_block: int = 0, max_candidates: int = 0, window_bytes: int = 0,
+                      links: bool = True, size: Optional[int] = None) -> DatFileCheck:
+        """Check a storage data file on the device (K14 scan and parse, K8 /
+        K8s inflate, K6 VerifyBlock; hbx_datfile_check_path / _device): every
+        good entry RecoverData's walk finds, every gap and broken span and
+        where to truncate.  ``source`` is a path, the file's bytes, or a device
+        pointer (then ``size`` is required; the image needs 64 readable bytes
+        behind it).  Nothing is written or repaired.  The output arrays are
+        sized from a first guess and, when the file holds more, from the counts
+        the library reports (the check then runs once more)."""
+        d, n, path, arena = self._dat_image(source, size)
+        try:
+            guess = (n if path is None else os.path.getsize(path)) // 29 + 1
+            ecap = scap = min(guess, 1 << 16)
+            lcap = min(guess, 1 << 16) if links else 0
+            cands = int(max_candidates)
+            sm = _lib.DatSummary()
+            for _ in range(3):
+                ents = (_lib.DatEntry * max(ecap, 1))()
+                spans = (_lib.DatSpan * max(scap, 1))()
+                lk = np.zeros((max(lcap, 1), 16), np.uint8)
+                tail = (ents, ecap, spans, scap, _p(lk) if links else None, lcap, ctypes.byref(sm))
+                if path is not None:
+                    rc = self._L.hbx_datfile_check_path(self._ctx, path, int(max_block), cands, int(window_bytes), *tail)
+                else:
+                    rc = self._L.hbx_datfile_check_device(self._ctx, d, n, int(max_block), cands, int(window_bytes), *tail)
+                if rc != _lib.ERR_CAPACITY:
+                    break
+                # hbx_last_error names what did not fit; the summary has the counts
+                need_c = max(int(sm.n_candidates), int(sm.n_gap_markers))
+                if need_c > (cands or (1 << 20)):
+                    if max_candidates:
+                        break  # the caller set the capacity: the error is theirs
+                    cands = need_c
+                elif sm.n_entries > ecap or sm.n_spans > scap or (links and sm.n_links > lcap):
+                    ecap, scap = max(ecap, int(sm.n_entries)), max(scap, int(sm.n_spans))
+                    lcap = max(lcap, int(sm.n_links)) if links else 0
+                else:
+                    break
+            self._check(rc, "hbx_datfile_check")
+        finally:
+            if arena is not None:
+                self._L.hbx_arena_free(self._ctx, arena)
+        ne, ns, nl = int(sm.n_entries), int(sm.n_spans), int(sm.n_links)
+        ev = np.ctypeslib.as_array(ents)[:ne]
+        e = np.zeros(ne, DAT_ENTRY_DTYPE)
+        for name in DAT_ENTRY_DTYPE.names:
+            e[name] = ev[name]
+        sv = np.ctypeslib.as_array(spans)[:ns]
+        s = np.zeros(ns, DAT_SPAN_DTYPE)
+        for name in DAT_SPAN_DTYPE.names:
+            s[name] = sv[name]
+        summary = {k: int(getattr(sm, k)) for k, _ in _lib.DatSummary._fields_}
+        if summary["truncate_at"] == _lib.NO_DIFF:
+            summary["truncate_at"] = None
+        return DatFileCheck(e, s, summary, lk[:nl].copy() if links else None)
+
+    def verify_datfile_at(self, source, offs: Sequence[int], expect_ids, content: bool = True, max_block: int = 0,
+                          window_bytes: int = 0, size: Optional[int] = None) -> np.ndarray:
+        """The entries of a data file at offsets the index names
+        (checkBlockFromIXEntry, integrity.go:259-296; hbx_datfile_verify_at):
+        uint32 per offset, 9 = no structurally valid entry there, 10 = not the
+        expected BlockID, else the VerifyBlock status (0 good) with ``content``
+        or 0 for the header and ID check alone.  ``source`` as
+        :meth:`check_datfile`."""
+        o = np.ascontiguousarray(np.asarray(offs, np.uint64).reshape(-1))
+        n = int(o.shape[0])
+        want = _ids_array(expect_ids) if n else np.zeros((0, 16), np.uint8)
+        if want.shape[0] != n:
+            raise ValueError("one expected ID per offset")
+        st = np.zeros(max(n, 1), np.uint32)
+        d, sz, path, arena = self._dat_image(source, size)
+        try:
+            self._check(self._L.hbx_datfile_verify_at(self._ctx, d, sz, path, n, _p(o), _p(want), 1 if content else 0,
+                                                      int(max_block), int(window_bytes), _p(st)),
+                        "hbx_datfile_verify_at")
+        finally:
+            if arena is not None:
+                self._L.hbx_arena_free(self._ctx, arena)
+        return st[:n]
 
     def match_paths(self, paths: Sequence[Union[str, os.PathLike]], chains_ids, io_threads: int = 16,
                     batch_bytes: int = 1 << 30, sizes: Optional[Sequence[int]] = None,

@@ -1007,6 +1007,187 @@ int hbx_locate_ids(hbx_ctx *ctx, uint64_t n_pool_files, const uint64_t *pool_fir
                    const uint8_t *pool_ids, const uint64_t *pool_cut_ends,
                    uint64_t n_want, const uint8_t *want_ids, hbx_block_loc *loc, uint64_t *n_found);
 
+/* ---- Check a storage data file: scan, inflate, verify (K14) ---------------------
+ * The server keeps its blocks in data files (*.dat, pkg/storagedb/data.go,
+ * storagedb.go:40-53):
+ *   header  BE32 filetype "HSDB" | BE32 version 1 | BE64 deadspace     (16 bytes)
+ *   entry   "hblk" | BlockID[16] | BE32 n_links | n_links x 16 | DataType u8 |
+ *           BE32 data_len | data            (data.go:33-37 around block.go:56-94;
+ *           size = 29 + 16 n_links + data_len)
+ *   gap     "Cgap" | BE64 skip, counted from the 'C'            (data.go:142-164)
+ * RecoverData (integrity.go:74-143) walks a file from offset 16, one block at a
+ * time on one goroutine, and resynchronises after damage on the next "hblk"
+ * anywhere in the bytes; checkBlockFromIXEntry (integrity.go:259-296) reads the
+ * entry at an offset the index names.  These calls do both on the device: K14
+ * (hbx_k14_scan, hbx_k14_parse) finds and frames every "hblk" and "Cgap" of
+ * the image, K8 / K8s and K6 inflate and VerifyBlock every framed entry in
+ * place, links in the hash, and the walk is left with list lookups
+ * (hbx_datfile_walk).  They report and write nothing: repairing index and meta
+ * files, rewriting blocks and writing gap markers stay with the caller.
+ *
+ * The walk.  offset = 16; while offset < size:
+ *   1. fewer than 12 bytes left: a failure at offset.  Else, "Cgap" at offset
+ *      with skip > 0: a gap of skip bytes, offset += skip.  A skip past the end
+ *      of the file ends the gap (and the walk) at the end and sets gap_past_eof.
+ *      (The reference does not terminate on such a file: its reader discards
+ *      nothing more at the end and the loop in skipDataGap goes on, data.go:157.)
+ *      A gap that ends exactly at the end of the file ends the walk.  Only ONE
+ *      marker is skipped per step: a gap behind a gap is read as an entry and
+ *      fails, as it does in the reference.  skip <= 0 skips nothing.
+ *   2. blockOffset = offset.
+ *   3. The entry at blockOffset is STRUCTURALLY VALID if the marker is there,
+ *      every field lies inside the file (n_links and data_len are untrusted:
+ *      64-bit arithmetic), DataType is raw or zlib and data_len <=
+ *      hbx_restore_in_bound(max_block).
+ *   4. It is GOOD if it is structurally valid and VerifyBlock is true (status
+ *      0 of hbx_restore_blocks); then offset = blockOffset + size.
+ *   5. Any failure opens a broken span at blockOffset unless one is open, and
+ *      the walk goes on at the first "hblk" at a position > blockOffset, also
+ *      one inside the failed entry's claimed extent; without one it ends.
+ *   6. A broken span runs to the next good entry's offset; consecutive failures
+ *      merge; a walk that ends inside one sets truncate_at to its start
+ *      (integrity.go:250-253).
+ * Every result satisfies 16 + sum(entry sizes) + sum(gap lengths) + sum(broken
+ * span lengths) = size (for size >= 16). */
+#define HBX_DAT_FILETYPE 0x48534442u /* "HSDB" */
+#define HBX_DAT_VERSION 1u
+#define HBX_DAT_HEADER 16u
+#define HBX_DAT_MARKER 0x68626C6Bu /* "hblk" */
+#define HBX_DAT_GAP 0x43676170u    /* "Cgap" */
+#define HBX_DAT_ENTRY_MIN 29u      /* an entry without links and data */
+#define HBX_DAT_IMAGE_SLACK 64u    /* readable bytes a device image needs behind its size */
+#define HBX_DAT_ST_INVALID 9u      /* no marker, or not structurally valid */
+#define HBX_DAT_ST_WRONG_ID 10u    /* hbx_datfile_verify_at: not the expected BlockID */
+#define HBX_DAT_F_MARKER 1u        /* hbx_dat_record.flags: the 4-byte marker is at off */
+#define HBX_DAT_F_GAP 2u           /* the record frames a gap marker; size holds the skip */
+#define HBX_DAT_SPAN_GAP 0u
+#define HBX_DAT_SPAN_BROKEN 1u
+typedef struct {
+  uint64_t off;       /* the position framed */
+  uint64_t size;      /* 29 + 16 n_links + data_len; a gap: its skip as two's complement */
+  uint64_t data_off;  /* where the data field starts in the file */
+  uint64_t links_off; /* where the links start (off + 24) */
+  uint32_t data_len;
+  uint32_t n_links;
+  uint32_t status;    /* 0: structurally valid (after the check: the VerifyBlock status); 9 */
+  uint8_t type;       /* DataType */
+  uint8_t flags;      /* HBX_DAT_F_* */
+  uint16_t pad;
+  uint8_t id[16];     /* BlockID */
+} hbx_dat_record;     /* 64 bytes, what hbx_k14_parse writes; but for off and flags all 0 when status is 9 */
+typedef struct {
+  uint64_t off, size, data_off;
+  uint64_t link_base; /* index of its first link in the links output (16 bytes each) */
+  uint32_t n_links, data_len;
+  uint32_t plain_len; /* length of the block's data after inflating */
+  uint8_t type;
+  uint8_t pad[3];
+  uint8_t id[16];
+} hbx_dat_entry;      /* 64 bytes: a good entry on the walk */
+typedef struct {
+  uint64_t off, len;
+  uint32_t kind;      /* HBX_DAT_SPAN_GAP / HBX_DAT_SPAN_BROKEN */
+  uint32_t status;    /* broken: status of its first failure (1..8 as hbx_restore_blocks, 9); gap: 0 */
+  uint64_t n_failed;  /* broken: failures inside at positions that carry the "hblk" marker */
+} hbx_dat_span;       /* 32 bytes */
+typedef struct {
+  uint64_t size;
+  uint32_t filetype, version; /* header fields (0 where the file is too short) */
+  uint64_t deadspace;
+  uint32_t header_ok;         /* 16 bytes, "HSDB", version 1 */
+  uint32_t gap_past_eof;
+  uint64_t n_candidates;      /* "hblk" markers at positions in [16, size - 4] */
+  uint64_t n_gap_markers;     /* "Cgap" markers there */
+  uint64_t n_valid;           /* structurally valid candidates: each was inflated and verified */
+  uint64_t n_unreached;       /* candidates that never were the walk's block offset */
+  uint64_t n_entries, entry_bytes;
+  uint64_t n_gaps, gap_bytes;
+  uint64_t n_broken, broken_bytes;
+  uint64_t n_spans;           /* n_gaps + n_broken */
+  uint64_t n_links;           /* links of all good entries */
+  uint64_t truncate_at;       /* UINT64_MAX: the walk did not end inside a broken span */
+} hbx_dat_summary;            /* 136 bytes */
+
+/* Pure host functions (no context, no device): the header, the structural
+ * rules and the walk, as the device path applies them.
+ * header_parse: in[0 .. len) is the start of a file.  HBX_OK for 16 bytes of
+ * "HSDB" version 1, HBX_ERR_FORMAT otherwise; the fields (each may be NULL)
+ * are written as far as len allows, else 0. */
+int hbx_datfile_header_parse(const uint8_t *in, uint64_t len, uint32_t *filetype, uint32_t *version,
+                             uint64_t *deadspace);
+/* Frame the entry at off of the file image[0 .. size) (host memory) by rule 3,
+ * exactly as hbx_k14_parse: no byte at or past size is read, whatever n_links
+ * and data_len claim.  rec->status is 0 or 9.  HBX_ERR_ARG for NULL arguments
+ * or max_block above 1 GiB (0 = HBX_MAX_BLOCK). */
+int hbx_datfile_entry_parse(const uint8_t *image, uint64_t size, uint64_t off, uint64_t max_block,
+                            hbx_dat_record *rec);
+/* The walk over a file of `size` bytes: cand[0 .. n_cand) the records of ALL
+ * its "hblk" positions, ascending by off, status 0 (good), 1..8 or 9;
+ * plain_len (may be NULL) parallel to cand; gap_offs ascending with gap_skips
+ * the "Cgap" positions that have 12 bytes inside the file.  Writes up to
+ * entry_cap entries and span_cap spans (both ascending by off; either array
+ * may be NULL with capacity 0) and *summary's walk fields (n_unreached,
+ * n_entries .. truncate_at, gap_past_eof, size, n_candidates, n_gap_markers;
+ * the header fields and n_valid are left alone).  HBX_ERR_CAPACITY if a
+ * capacity is too small: the summary then holds the needed counts.
+ * HBX_ERR_ARG for NULL lists with a count, a NULL summary or lists that do not
+ * ascend. */
+int hbx_datfile_walk(uint64_t size, uint64_t n_cand, const hbx_dat_record *cand, const uint32_t *plain_len,
+                     uint64_t n_gaps, const uint64_t *gap_offs, const int64_t *gap_skips,
+                     hbx_dat_entry *entries, uint64_t entry_cap, hbx_dat_span *spans, uint64_t span_cap,
+                     hbx_dat_summary *summary);
+/* Check the data file whose `size` bytes lie at d_image in device memory (16-byte
+ * aligned, HBX_DAT_IMAGE_SLACK readable bytes behind size; hbx_arena_alloc
+ * gives both).  max_block (0 = HBX_MAX_BLOCK) is the largest block data
+ * accepted; max_candidates (0 = 1 Mi) the capacity of each of K14's two
+ * position lists; window_bytes (0 = an eighth of the free device memory, at
+ * least 1 GiB, at most 32 GiB) bounds the inflate slots of one window by
+ * hbx_restore_many_window's rule, a zlib entry's share being
+ * min(max_block, 8 data_len + 4096): a stream that outgrows it is inflated
+ * again into a max_block slot, so no result depends on that estimate.  EVERY
+ * structurally valid candidate is inflated and verified, not only those the
+ * walk reaches, so the walk does not wait for a verification.  Inflated bytes
+ * are dropped after the hash.  Outputs: entries (entry_cap), spans (span_cap),
+ * links (16-byte IDs, link_cap of them; NULL with link_cap 0: not wanted) and
+ * *summary (required).  A damaged file is a result, not an error (HBX_OK).
+ * HBX_ERR_CAPACITY: more markers of a kind than max_candidates (then
+ * n_candidates / n_gap_markers hold the counts and nothing else is set), or
+ * more entries, spans or links than their capacities (then the summary is
+ * complete and the arrays hold what fitted).  HBX_ERR_ARG: NULL context,
+ * image or summary, an unaligned image, max_block above 1 GiB.  Synchronous;
+ * HBX_ERR_STATE while batches are pending; every stream is idle on return and
+ * the context stays usable after any failure.  Device memory beside the image:
+ * 16 bytes per list position + 72 per candidate + the window's slots, kept for
+ * the next call and freed by hbx_ctx_destroy.  Replaces the loop of
+ * RecoverData (integrity.go:94-143) up to its repairs, and CompactFile's
+ * sequential read of a data file. */
+int hbx_datfile_check_device(hbx_ctx *ctx, const void *d_image, uint64_t size, uint64_t max_block,
+                             uint64_t max_candidates, uint64_t window_bytes, hbx_dat_entry *entries,
+                             uint64_t entry_cap, hbx_dat_span *spans, uint64_t span_cap, uint8_t *links,
+                             uint64_t link_cap, hbx_dat_summary *summary);
+/* The same for the file at `path`: read through two pinned staging buffers
+ * into one device image.  HBX_ERR_IO (with the path in hbx_last_error) if it
+ * cannot be opened or read in full; HBX_ERR_CAPACITY if it does not fit a
+ * third of the free device memory (segmenting is the caller's business). */
+int hbx_datfile_check_path(hbx_ctx *ctx, const char *path, uint64_t max_block, uint64_t max_candidates,
+                           uint64_t window_bytes, hbx_dat_entry *entries, uint64_t entry_cap,
+                           hbx_dat_span *spans, uint64_t span_cap, uint8_t *links, uint64_t link_cap,
+                           hbx_dat_summary *summary);
+/* Entries at offsets the caller knows (checkBlockFromIXEntry, integrity.go:
+ * 259-296): no scan, no walk.  The image is d_image (size bytes, as above) or,
+ * with d_image NULL, the file at path (then size is ignored).  status[i] for
+ * offs[i] with the expected BlockID expect_ids[16 i ..]:
+ *   9   no structurally valid entry there;
+ *   10  the entry's BlockID is not the expected one (integrity.go:292);
+ *   else, content != 0: the VerifyBlock status (0..7; fullVerify,
+ *   integrity.go:279-284); content == 0: 0, the header and ID check alone
+ *   (integrity.go:287-295).
+ * Errors and the contract as hbx_datfile_check_device / _path; n == 0 is
+ * HBX_OK and nothing runs. */
+int hbx_datfile_verify_at(hbx_ctx *ctx, const void *d_image, uint64_t size, const char *path, uint64_t n,
+                          const uint64_t *offs, const uint8_t *expect_ids, int content, uint64_t max_block,
+                          uint64_t window_bytes, uint32_t *status);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
