@@ -46,6 +46,7 @@ EXPORTS = [
     "hbx_k1_summaries", "hbx_locate_ids",
     "hbx_datfile_header_parse", "hbx_datfile_entry_parse", "hbx_datfile_walk",
     "hbx_datfile_check_device", "hbx_datfile_check_path", "hbx_datfile_verify_at",
+    "hbx_block_graph",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -171,6 +172,15 @@ class DatSummary(ctypes.Structure):
                 ("truncate_at", ctypes.c_uint64)]
 
 
+class GraphSummary(ctypes.Structure):
+    """hbx_graph_summary: what hbx_block_graph found (K15)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_rows", "n_links", "n_alias", "n_missing_links", "n_roots", "n_roots_missing", "n_marked", "mark_levels",
+        "n_faulty", "n_invalid", "fault_levels", "n_marked_faulty")]
+
+
+GRAPH_NONE = 0xFFFFFFFF             # HBX_GRAPH_NONE
+GRAPH_LANE_MAX, GRAPH_WAVE_MAX = 16, 4096  # HBX_GRAPH_LANE_MAX, HBX_GRAPH_WAVE_MAX (hbx_knobs reports them)
 DAT_HEADER, DAT_IMAGE_SLACK = 16, 64            # HBX_DAT_HEADER, HBX_DAT_IMAGE_SLACK
 DAT_ST_INVALID, DAT_ST_WRONG_ID = 9, 10         # HBX_DAT_ST_*
 DAT_F_MARKER, DAT_F_GAP = 1, 2                  # HBX_DAT_F_*
@@ -323,6 +333,7 @@ def load() -> ctypes.CDLL:
     L.hbx_datfile_check_path.argtypes = [P, ctypes.c_char_p, U64, U64, U64, P, U64, P, U64, P, U64,
                                          ctypes.POINTER(DatSummary)]
     L.hbx_datfile_verify_at.argtypes = [P, P, U64, ctypes.c_char_p, U64, P, P, I, U64, U64, P]
+    L.hbx_block_graph.argtypes = [P, U64, P, P, P, U64, P, P, U64, P, P, P, P, P, P, ctypes.POINTER(GraphSummary)]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

@@ -46,6 +46,7 @@
 #include "hbx_restore.hip"
 #include "hbx_restore_many.hip"
 #include "hbx_datfile.hip"
+#include "hbx_graph.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 #include "hbx_datfile.h"
@@ -460,6 +461,9 @@ struct hbx_ctx {
   PinBuf h_dfstage[2];
   uint32_t k14_wgs = 0;
   uint64_t dat_windows = 0, dat_retries = 0;
+  // hbx_block_graph (bg_layout names the buffers); K15's workgroup cap (0 = by size; HBX_K15_WGS: tests)
+  DevBuf d_bg[16];
+  uint32_t k15_wgs = 0;
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -1900,6 +1904,8 @@ int hbx_ctx_create(int device, hbx_ctx** out) {
   if (const char* v = ab_env("HBX_K3_WGS")) c->md5_wgs = (uint32_t)std::min<int>(std::max(1, ncu), std::max(1, std::atoi(v)));
   // (tests: a K14 grid of one or two workgroups, so a small image spans several grid-stride rounds)
   if (const char* v = ab_env("HBX_K14_WGS")) c->k14_wgs = (uint32_t)std::min(65536, std::max(0, std::atoi(v)));
+  // (tests: a K15 grid of one or two workgroups, so a small table spans several grid-stride rounds)
+  if (const char* v = ab_env("HBX_K15_WGS")) c->k15_wgs = (uint32_t)std::min(65536, std::max(0, std::atoi(v)));
   if (hipSetDevice(device) != hipSuccess || make_stream(&c->stream, "HBX_SCAN_CUS", ncu, "0:4096") != hipSuccess) {
     delete c;
     return HBX_ERR_HIP;
@@ -1978,6 +1984,7 @@ void hbx_ctx_destroy(hbx_ctx* c) {
   c->d_mtout.release();
   for (DevBuf& d : c->d_lc) d.release();
   for (DevBuf& d : c->d_df) d.release();
+  for (DevBuf& d : c->d_bg) d.release();
   c->d_dfimg.release();
   for (PinBuf& h : c->h_dfstage) h.release();
   for (hbx_seg* h : c->segs_open) delete h;
@@ -2157,7 +2164,8 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"k8_split_fallbacks\": %llu, \"gate_meta\": %u, \"sdma_warm\": %u, \"sdma_h2d_mask\": %u, "
       "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
       "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu], "
-      "\"match_push_bytes\": %llu, \"k14_wgs\": %u, \"datfile\": [%llu, %llu]}",
+      "\"match_push_bytes\": %llu, \"k14_wgs\": %u, \"datfile\": [%llu, %llu], \"k15_wgs\": %u, "
+      "\"k15_lane_max\": %u, \"k15_wave_max\": %u}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
@@ -2166,7 +2174,7 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3],
       (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries,
       (unsigned long long)c->match_push_bytes, c->k14_wgs, (unsigned long long)c->dat_windows,
-      (unsigned long long)c->dat_retries);
+      (unsigned long long)c->dat_retries, c->k15_wgs, hbxg::kLaneMax, hbxg::kWaveMax);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -2460,6 +2468,217 @@ int hbx_locate_ids(hbx_ctx* c, uint64_t nf, const uint64_t* pool_first, const ui
   HBX_TRY(c, hipStreamSynchronize(s));
   if (n_found) *n_found = found;
   return HBX_OK;
+}
+
+// ---- K15: the block graph (DESIGN.md §5 "K15", hbx_graph.hip) --------------
+namespace {
+// hbx_ctx::d_bg
+enum {
+  kBgIds, kBgNLinks, kBgBase, kBgBad, kBgLinks, kBgRoots, kBgTable, kBgRep, kBgLinkRow, kBgRootRow, kBgMark,
+  kBgFault, kBgFrontier, kBgCounts, kBgRend, kBgRsrc, kBgBufs
+};
+static_assert(kBgBufs == 16, "hbx_ctx::d_bg");
+
+// One sweep from the frontier in front[0] (n_front rows at depth 0), a launch
+// per level; *levels = the levels that held a row.
+int bg_sweep(hbx_ctx* c, hipStream_t s, const hbxg::Graph& g, uint32_t* depth, uint32_t* front[2], uint64_t n_front,
+             unsigned long long* d_cnt, uint64_t n, uint64_t* levels) {
+  uint32_t level = 0;
+  *levels = 0;
+  while (n_front && level <= n) {  // (a level claims at least one row: at most n levels)
+    *levels = (uint64_t)level + 1;
+    HBX_TRY(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
+    const hbxg::ExpandArgs ea{g, front[level & 1], n_front, depth, level, front[(level + 1) & 1], d_cnt, n};
+    hipLaunchKernelGGL(hbx_k15_expand, dim3(hbxg::grid(n_front, c->k15_wgs)), dim3(hbxg::kThreads), 0, s, ea);
+    HBX_TRY(c, hipGetLastError());
+    unsigned long long next = 0;
+    HBX_TRY(c, hipMemcpyAsync(&next, d_cnt, sizeof(next), hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    n_front = std::min<uint64_t>(next, n);
+    level++;
+  }
+  return HBX_OK;
+}
+}  // namespace
+
+static_assert(sizeof(hbx_graph_summary) == 96, "hbx_graph_summary is twelve uint64");
+
+int hbx_block_graph(hbx_ctx* c, uint64_t n, const uint8_t* ids, const uint32_t* n_links, const uint64_t* link_base,
+                    uint64_t m, const uint8_t* links, const uint8_t* bad, uint64_t n_roots, const uint8_t* root_ids,
+                    uint32_t* rep, uint32_t* link_row, uint32_t* root_row, uint32_t* mark_depth,
+                    uint32_t* fault_depth, hbx_graph_summary* sum) {
+  if (!c || !sum) return HBX_ERR_ARG;
+  if (n > 0x7FFFFFFFull || (n && (!ids || !n_links || !link_base)) || (m && !links) || (n_roots && !root_ids))
+    return HBX_ERR_ARG;
+  uint64_t sum_links = 0;  // bounds the transposed graph
+  for (uint64_t i = 0; i < n; i++) {
+    if (link_base[i] > m || n_links[i] > m - link_base[i]) return HBX_ERR_ARG;
+    sum_links += n_links[i];
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  std::memset(sum, 0, sizeof(*sum));
+  sum->n_rows = n;
+  sum->n_links = m;
+  sum->n_roots = n_roots;
+  if (n == 0) {  // nothing to look anything up in
+    if (link_row) std::fill(link_row, link_row + m, hbxg::kNone);
+    if (root_row) std::fill(root_row, root_row + n_roots, hbxg::kNone);
+    sum->n_missing_links = m;
+    sum->n_roots_missing = n_roots;
+    return HBX_OK;
+  }
+  HBX_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->rstream;
+  const bool run_mark = mark_depth || n_roots, run_tree = fault_depth != nullptr;
+  const uint64_t slots = hbxd::table_slots(n), chunks = (n + hbxg::kScanChunk - 1) / hbxg::kScanChunk;
+  size_t need[kBgBufs] = {};
+  need[kBgIds] = n * 16;
+  need[kBgNLinks] = n * 4;
+  need[kBgBase] = n * 8;
+  need[kBgBad] = bad ? n : 0;
+  need[kBgLinks] = m * 16;
+  need[kBgRoots] = n_roots * 16;
+  need[kBgTable] = slots * sizeof(uint32_t);
+  need[kBgRep] = n * 4;
+  need[kBgLinkRow] = m * 4;
+  need[kBgRootRow] = n_roots * 4;
+  need[kBgMark] = run_mark ? n * 4 : 0;
+  need[kBgFault] = run_tree ? n * 4 : 0;
+  need[kBgFrontier] = 2 * n * 4;
+  need[kBgCounts] = hbxg::kCntWords * sizeof(unsigned long long);
+  // (the transposed graph is sized when a faulty row turns up)
+  auto fits = [&](std::initializer_list<int> which) -> int {
+    uint64_t grow = 0;
+    for (int b : which)
+      if (need[b] > c->d_bg[b].cap) grow += need[b] + 4096 - c->d_bg[b].cap;
+    size_t fr = 0, tot = 0;
+    HBX_TRY(c, hipMemGetInfo(&fr, &tot));
+    if (grow > fr)
+      return c->fail(HBX_ERR_CAPACITY, "hbx_block_graph: the table needs " + std::to_string(grow) +
+                                           " more bytes of device memory, " + std::to_string(fr) + " are free");
+    for (int b : which) HBX_TRY(c, c->d_bg[b].ensure(need[b]));
+    return HBX_OK;
+  };
+  if (int rc = fits({kBgIds, kBgNLinks, kBgBase, kBgBad, kBgLinks, kBgRoots, kBgTable, kBgRep, kBgLinkRow, kBgRootRow,
+                     kBgMark, kBgFault, kBgFrontier, kBgCounts}))
+    return rc;
+  const uint4* d_ids = c->d_bg[kBgIds].as<uint4>();
+  const uint32_t* d_nl = c->d_bg[kBgNLinks].as<uint32_t>();
+  const uint64_t* d_base = c->d_bg[kBgBase].as<uint64_t>();
+  const uint8_t* d_bad = bad ? c->d_bg[kBgBad].as<uint8_t>() : nullptr;
+  uint32_t* d_table = c->d_bg[kBgTable].as<uint32_t>();
+  uint32_t* d_rep = c->d_bg[kBgRep].as<uint32_t>();
+  uint32_t* d_lrow = c->d_bg[kBgLinkRow].as<uint32_t>();
+  uint32_t* d_rrow = c->d_bg[kBgRootRow].as<uint32_t>();
+  uint32_t* d_mark = run_mark ? c->d_bg[kBgMark].as<uint32_t>() : nullptr;
+  uint32_t* d_fault = run_tree ? c->d_bg[kBgFault].as<uint32_t>() : nullptr;
+  uint32_t* front[2] = {c->d_bg[kBgFrontier].as<uint32_t>(), c->d_bg[kBgFrontier].as<uint32_t>() + n};
+  unsigned long long* d_cnt = c->d_bg[kBgCounts].as<unsigned long long>();
+  const uint32_t wgs = c->k15_wgs, mask = (uint32_t)(slots - 1);
+  const dim3 block(hbxg::kThreads);
+  // the frontier's length after the launch that filled it
+  auto frontier_len = [&](uint64_t* len) -> int {
+    unsigned long long v = 0;
+    HBX_TRY(c, hipMemcpyAsync(&v, d_cnt + hbxg::kCntFrontier, sizeof(v), hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    *len = std::min<uint64_t>(v, n);
+    return HBX_OK;
+  };
+  const int rc = [&]() -> int {
+    HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgIds].p, ids, n * 16, hipMemcpyHostToDevice, s));
+    HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgNLinks].p, n_links, n * 4, hipMemcpyHostToDevice, s));
+    HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgBase].p, link_base, n * 8, hipMemcpyHostToDevice, s));
+    if (bad) HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgBad].p, bad, n, hipMemcpyHostToDevice, s));
+    if (m) HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgLinks].p, links, m * 16, hipMemcpyHostToDevice, s));
+    if (n_roots) HBX_TRY(c, hipMemcpyAsync(c->d_bg[kBgRoots].p, root_ids, n_roots * 16, hipMemcpyHostToDevice, s));
+    HBX_TRY(c, hipMemsetAsync(d_cnt, 0, hbxg::kCntWords * sizeof(unsigned long long), s));
+    // 1. the table: K13's build over the rows' IDs as they are
+    HBX_TRY(c, hipMemsetAsync(d_table, 0, slots * sizeof(uint32_t), s));
+    const hbxl::Args la{d_ids, nullptr, nullptr, nullptr, d_table, nullptr, nullptr, (uint32_t)n, 0u, 0u, mask};
+    hipLaunchKernelGGL(hbx_k13_build, dim3((uint32_t)((n + hbxl::kThreads - 1) / hbxl::kThreads)),
+                       dim3(hbxl::kThreads), 0, s, la);
+    HBX_TRY(c, hipGetLastError());
+    // 2. resolve: the rows' own IDs (rep), the links, the roots
+    const hbxg::ResolveArgs rs[3] = {
+        {d_ids, d_table, d_ids, d_rep, d_cnt + hbxg::kCntAlias, n, (uint32_t)n, mask, 1u},
+        {d_ids, d_table, c->d_bg[kBgLinks].as<uint4>(), d_lrow, d_cnt + hbxg::kCntMissLinks, m, (uint32_t)n, mask, 0u},
+        {d_ids, d_table, c->d_bg[kBgRoots].as<uint4>(), d_rrow, d_cnt + hbxg::kCntMissRoots, n_roots, (uint32_t)n,
+         mask, 0u}};
+    for (const hbxg::ResolveArgs& ra : rs)
+      if (ra.n_keys) hipLaunchKernelGGL(hbx_k15_resolve, dim3(hbxg::grid(ra.n_keys, wgs)), block, 0, s, ra);
+    HBX_TRY(c, hipGetLastError());
+    const hbxg::Graph fwd{d_base, d_nl, nullptr, d_lrow};
+    // 3. mark: the roots at depth 0, then a launch per level
+    if (run_mark) {
+      HBX_TRY(c, hipMemsetAsync(d_mark, 0xFF, n * 4, s));
+      uint64_t n_front = 0;
+      if (n_roots) {
+        const hbxg::RootArgs ra{d_rrow, n_roots, d_mark, front[0], d_cnt + hbxg::kCntFrontier, n};
+        hipLaunchKernelGGL(hbx_k15_roots, dim3(hbxg::grid(n_roots, wgs)), block, 0, s, ra);
+        HBX_TRY(c, hipGetLastError());
+        if (int e = frontier_len(&n_front)) return e;
+      }
+      if (int e = bg_sweep(c, s, fwd, d_mark, front, n_front, d_cnt + hbxg::kCntFrontier, n, &sum->mark_levels)) return e;
+    }
+    // 4. tree check: the faulty rows at depth 0; only with one of them the transposed graph and its sweep
+    if (run_tree) {
+      HBX_TRY(c, hipMemsetAsync(d_fault, 0xFF, n * 4, s));
+      HBX_TRY(c, hipMemsetAsync(d_cnt + hbxg::kCntFrontier, 0, sizeof(unsigned long long), s));
+      hbxg::RowArgs wa{fwd, d_rep, d_bad, d_fault, front[0], d_cnt + hbxg::kCntFrontier, nullptr, nullptr, n, (uint32_t)n};
+      hipLaunchKernelGGL(hbx_k15_seed, dim3(hbxg::grid(n, wgs)), block, 0, s, wa);
+      HBX_TRY(c, hipGetLastError());
+      if (int e = frontier_len(&sum->n_faulty)) return e;
+      if (sum->n_faulty) {
+        need[kBgRend] = (n + chunks) * 8;
+        need[kBgRsrc] = sum_links * 4;
+        if (int e = fits({kBgRend, kBgRsrc})) return e;
+        unsigned long long* d_rend = c->d_bg[kBgRend].as<unsigned long long>();
+        unsigned long long* d_sums = d_rend + n;
+        HBX_TRY(c, hipMemsetAsync(d_rend, 0, n * 8, s));
+        wa.cursor = d_rend;
+        wa.rsrc = c->d_bg[kBgRsrc].as<uint32_t>();
+        wa.cap = sum_links;
+        hipLaunchKernelGGL(hbx_k15_indeg, dim3(hbxg::grid(n, wgs)), block, 0, s, wa);
+        hipLaunchKernelGGL(hbx_k15_scan_sums, dim3((uint32_t)chunks), block, 0, s, d_rend, n, d_sums);
+        hipLaunchKernelGGL(hbx_k15_scan_top, dim3(1), block, 0, s, d_sums, chunks);
+        hipLaunchKernelGGL(hbx_k15_scan_add, dim3((uint32_t)chunks), block, 0, s, d_rend, n, d_sums);
+        hipLaunchKernelGGL(hbx_k15_fill, dim3(hbxg::grid(n, wgs)), block, 0, s, wa);
+        HBX_TRY(c, hipGetLastError());
+        const hbxg::Graph back{nullptr, nullptr, reinterpret_cast<const uint64_t*>(d_rend), wa.rsrc};
+        if (int e = bg_sweep(c, s, back, d_fault, front, sum->n_faulty, d_cnt + hbxg::kCntFrontier, n,
+                             &sum->fault_levels))
+          return e;
+      }
+    }
+    // 5. finish: the aliases' depths, the counts
+    if (run_mark || run_tree) {
+      const hbxg::FinishArgs fa{d_rep, d_mark, d_fault, d_cnt, (uint32_t)n};
+      hipLaunchKernelGGL(hbx_k15_finish, dim3(hbxg::grid(n, wgs)), block, 0, s, fa);
+      HBX_TRY(c, hipGetLastError());
+    }
+    unsigned long long cnt[hbxg::kCntWords] = {};
+    if (rep) HBX_TRY(c, hipMemcpyAsync(rep, d_rep, n * 4, hipMemcpyDeviceToHost, s));
+    if (link_row && m) HBX_TRY(c, hipMemcpyAsync(link_row, d_lrow, m * 4, hipMemcpyDeviceToHost, s));
+    if (root_row && n_roots) HBX_TRY(c, hipMemcpyAsync(root_row, d_rrow, n_roots * 4, hipMemcpyDeviceToHost, s));
+    if (mark_depth) HBX_TRY(c, hipMemcpyAsync(mark_depth, d_mark, n * 4, hipMemcpyDeviceToHost, s));
+    if (fault_depth) HBX_TRY(c, hipMemcpyAsync(fault_depth, d_fault, n * 4, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipMemcpyAsync(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    sum->n_alias = cnt[hbxg::kCntAlias];
+    sum->n_missing_links = cnt[hbxg::kCntMissLinks];
+    sum->n_roots_missing = cnt[hbxg::kCntMissRoots];
+    sum->n_marked = cnt[hbxg::kCntMarked];
+    sum->n_invalid = cnt[hbxg::kCntInvalid];
+    sum->n_marked_faulty = cnt[hbxg::kCntMarkedFaulty];
+    return HBX_OK;
+  }();
+  if (rc != HBX_OK) {  // leave the stream idle and the error state clean: the context stays usable
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+  }
+  return rc;
 }
 
 int hbx_wait(hbx_ctx* c) {

@@ -107,6 +107,36 @@ class DatFileCheck:
     links: Optional[np.ndarray]  # uint8 [summary["n_links"], 16]: entry e's are links[link_base : link_base + n_links]
 
 
+GRAPH_NONE = _lib.GRAPH_NONE
+
+
+@dataclass(slots=True)
+class BlockGraph:
+    """What :meth:`Engine.block_graph` returns (hbx_block_graph): the block
+    table's links resolved to rows, the GC mark from the roots (MarkIndexes,
+    pkg/storagedb/gc.go:24-69) and the block-tree check (checkBlockFromIXEntry's
+    recursion, integrity.go:298-329).  ``GRAPH_NONE`` stands for no row and no
+    depth."""
+    rep: np.ndarray  # uint32 [n]: the lowest row carrying row i's ID
+    link_row: np.ndarray  # uint32 [m]: the representative row each link names, GRAPH_NONE = missing
+    root_row: np.ndarray  # uint32 [n_roots]: the same for the roots
+    mark_depth: np.ndarray  # uint32 [n]: links from the nearest root, GRAPH_NONE = unreached
+    fault_depth: np.ndarray  # uint32 [n]: links down to the nearest faulty row, GRAPH_NONE = the tree is valid
+    summary: dict  # hbx_graph_summary's fields
+
+    @property
+    def marked(self) -> np.ndarray:
+        return self.mark_depth != GRAPH_NONE
+
+    @property
+    def tree_ok(self) -> np.ndarray:
+        return self.fault_depth == GRAPH_NONE
+
+    @property
+    def alias(self) -> np.ndarray:
+        return self.rep != np.arange(self.rep.shape[0], dtype=np.uint32)
+
+
 def max_chunks(n: int) -> int:
     return n // MIN_BLOCK_SIZE + 1
 
@@ -596,6 +626,46 @@ class Engine:
         out = np.empty(nw, np.dtype([("file", np.uint32), ("chunk", np.uint32), ("off", np.uint64), ("len", np.uint64)]))
         for name in out.dtype.names:
             out[name] = v[name]
+        return out
+
+    def block_graph(self, ids, n_links, links, roots=None, bad=None, link_base=None) -> BlockGraph:
+        """K15 (hbx_block_graph): join a block table with its links on the
+        device.  ``ids`` are the rows' block IDs, ``n_links`` their link counts,
+        ``links`` the flat array of link IDs and ``link_base`` where each row's
+        list starts in it (None: the running sum of ``n_links``); ``bad`` marks
+        rows whose own check failed, ``roots`` are the IDs the GC mark starts
+        from.  IDs as :meth:`locate_ids` takes them.  :func:`formats.block_table`
+        makes the table from :meth:`check_datfile` results."""
+        idv = _ids_array(ids) if len(ids) else np.zeros((0, 16), np.uint8)
+        n = idv.shape[0]
+        nl = np.ascontiguousarray(np.asarray(n_links).reshape(-1), np.uint32)
+        lk = _ids_array(links) if len(links) else np.zeros((0, 16), np.uint8)
+        m = lk.shape[0]
+        rt = _ids_array(roots) if roots is not None and len(roots) else np.zeros((0, 16), np.uint8)
+        r = rt.shape[0]
+        if link_base is None:
+            lb = np.zeros(n, np.uint64)
+            if n > 1:
+                lb[1:] = np.cumsum(nl[:-1], dtype=np.uint64)
+        else:
+            lb = np.ascontiguousarray(np.asarray(link_base).reshape(-1), np.uint64)
+        if nl.shape[0] != n or lb.shape[0] != n:
+            raise ValueError("one link count and one link base per row")
+        bd = None
+        if bad is not None:
+            bd = np.ascontiguousarray(np.asarray(bad).reshape(-1) != 0, np.uint8)
+            if bd.shape[0] != n:
+                raise ValueError("one bad flag per row")
+        out = BlockGraph(np.zeros(n, np.uint32), np.zeros(m, np.uint32), np.zeros(r, np.uint32),
+                         np.zeros(n, np.uint32), np.zeros(n, np.uint32), {})
+        sm = _lib.GraphSummary()
+        # (an empty output still gets a pointer: NULL would mean "not wanted", here the mark and the check)
+        ptr = lambda a: a.ctypes.data  # noqa: E731
+        self._check(self._L.hbx_block_graph(self._ctx, n, _p(idv), _p(nl), _p(lb), m, _p(lk),
+                                            _p(bd) if bd is not None else None, r, _p(rt), ptr(out.rep),
+                                            ptr(out.link_row), ptr(out.root_row), ptr(out.mark_depth),
+                                            ptr(out.fault_depth), ctypes.byref(sm)), "hbx_block_graph")
+        out.summary = {k: int(getattr(sm, k)) for k, _ in _lib.GraphSummary._fields_}
         return out
 
     def _dat_image(self, source, size):

@@ -321,6 +321,36 @@ def store_tree(eng: Engine, root, reference_id: bytes = _ZERO16, io_threads: int
     return out
 
 
+def block_table(checks) -> tuple:
+    """The good entries of a store's data files as ONE block table for
+    :meth:`Engine.block_graph`: ``checks`` are the :class:`DatFileCheck` results
+    of the files in file order (checked with their links).  Returns ``(ids
+    uint8 [n, 16], n_links uint32 [n], link_base uint64 [n], links uint8 [m, 16],
+    file_no uint32 [n], off uint64 [n])``: each file's ``link_base`` is shifted
+    by the links of the files before it, and ``file_no`` / ``off`` say where a
+    row's entry lies (what an index entry holds).  With it "check every data
+    file, then mark from the roots" is ``check_datfile`` per file, this, and
+    ``block_graph``."""
+    ids, nl, lb, lk, fno, off = [], [], [], [], [], []
+    before = 0
+    for f, chk in enumerate(checks):
+        if chk.links is None:
+            raise ValueError(f"data file {f} was checked without its links")
+        e = chk.entries
+        ids.append(np.ascontiguousarray(e["id"], np.uint8).reshape(-1, 16))
+        nl.append(e["n_links"].astype(np.uint32))
+        lb.append(e["link_base"].astype(np.uint64) + np.uint64(before))
+        lk.append(np.ascontiguousarray(chk.links, np.uint8).reshape(-1, 16))
+        fno.append(np.full(e.shape[0], f, np.uint32))
+        off.append(e["off"].astype(np.uint64))
+        before += lk[-1].shape[0]
+
+    def cat(parts, dtype, tail=()):
+        return np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0,) + tail, dtype)
+    return (cat(ids, np.uint8, (16,)), cat(nl, np.uint32), cat(lb, np.uint64), cat(lk, np.uint8, (16,)),
+            cat(fno, np.uint32), cat(off, np.uint64))
+
+
 def _read_verified(eng: Engine, read_block, block_id: bytes, what: str) -> bytes:
     """ReadBlock + VerifyBlock of one directory or chain block: its data,
     inflated and hashed with its links on the device (Engine.restore_blocks)."""

@@ -1188,6 +1188,89 @@ int hbx_datfile_verify_at(hbx_ctx *ctx, const void *d_image, uint64_t size, cons
                           const uint64_t *offs, const uint8_t *expect_ids, int content, uint64_t max_block,
                           uint64_t window_bytes, uint32_t *status);
 
+/* ---- Block graph: GC mark and block-tree check (K15) -----------------------------
+ * hbx_datfile_check_* gives every good entry of a data file with its BlockID
+ * and its links.  The server joins that table next, one index probe and one
+ * meta read per block on one goroutine: MarkIndexes (pkg/storagedb/gc.go:24-69)
+ * follows links breadth-first from the roots and marks what it reaches;
+ * checkBlockFromIXEntry's link recursion (integrity.go:298-329, entered from
+ * CheckBlockTree :346-352 and CheckIndexes :354-410) calls a block valid only
+ * if its own check passed, every link exists and every linked block is valid.
+ * hbx_block_graph does both joins on the device (K15, hbx_graph.hip).
+ *
+ * Input: a BLOCK TABLE of n rows, ids[16 n], n_links[n], link_base[n], and a
+ * flat array of m link IDs.  Row i's links are links[16 (link_base[i] + k)] for
+ * k < n_links[i]; bases may come in any order, lists may overlap or leave
+ * holes.  bad[n] (may be NULL) is non-zero where the row's own check failed (a
+ * VerifyBlock status, an invalid index flag).  root_ids[16 n_roots] are the
+ * roots.  NONE = HBX_GRAPH_NONE.
+ *  1. Representative.  The node of an ID is its LOWEST row (K13's rule, so
+ *     every run answers the same); rep[i] is that row.  A row with rep[i] != i
+ *     is an ALIAS: its bad flag and its links are ignored, and its two depth
+ *     outputs are copies of its representative's.
+ *  2. Resolve.  link_row[e] is the representative row of links[e], or NONE (a
+ *     missing link), for every e < m, also for link slots no row owns;
+ *     root_row[q] the same for the roots.  Equality is on all 16 bytes.
+ *  3. Mark.  mark_depth[i] is the length of the shortest link path from any
+ *     root to row i: 0 for a root, NONE if unreached.  The links of bad rows
+ *     are followed too (the reference's mark does not look at validity).
+ *     Missing links and missing roots are skipped and counted: where the
+ *     reference aborts (gc.go:36-37) this call reports, and n_marked_faulty
+ *     lets a caller refuse to sweep.
+ *  4. Tree check.  A representative row is FAULTY if bad[i] is set or one of
+ *     its links is missing.  fault_depth[i] is 0 for a faulty row, else the
+ *     length of the shortest link path from row i down to a faulty row, else
+ *     NONE: the block tree below the row is valid, what verifiedBlocks[id] ==
+ *     true means in the reference.  Links that form a cycle cannot occur with
+ *     real MD5 IDs but can in a crafted table, and the reference recurses
+ *     without end on one; here a cycle from which no faulty row can be
+ *     reached is valid, and one from which a faulty row can be reached is not.
+ *  5. Summary.  Counts of rows count representatives only.  The levels of a
+ *     sweep are its largest depth + 1 (0 when it claimed no row).
+ * Every output is a function of the input alone: a depth is a BFS level,
+ * whichever lane claimed the row. */
+#define HBX_GRAPH_NONE 0xFFFFFFFFu
+#define HBX_GRAPH_LANE_MAX 16u   /* a link list up to this long is walked by one lane, */
+#define HBX_GRAPH_WAVE_MAX 4096u /* up to this long by its row's wave, a longer one by a workgroup */
+typedef struct {
+  uint64_t n_rows, n_links;  /* n and m as given */
+  uint64_t n_alias;          /* rows with rep[i] != i */
+  uint64_t n_missing_links;  /* e < m with link_row[e] == NONE */
+  uint64_t n_roots, n_roots_missing;
+  uint64_t n_marked;         /* representatives with mark_depth != NONE */
+  uint64_t mark_levels;
+  uint64_t n_faulty;         /* representatives with fault_depth == 0 */
+  uint64_t n_invalid;        /* representatives with fault_depth != NONE */
+  uint64_t fault_levels;
+  uint64_t n_marked_faulty;  /* representatives with both depths != NONE: a live tree is damaged */
+} hbx_graph_summary;         /* 96 bytes */
+/* All pointers are host memory, as in hbx_locate_ids.  Any output array (rep
+ * [n], link_row [m], root_row [n_roots], mark_depth [n], fault_depth [n]) may
+ * be NULL: not wanted.  With mark_depth == NULL and n_roots == 0 the mark does
+ * not run; with fault_depth == NULL the tree check does not run; the summary
+ * fields of a stage that did not run are 0 (n_marked_faulty needs both).  The
+ * transposed graph of the tree check is built only if a faulty row exists: a
+ * healthy store answers all-NONE after one pass over its links.
+ * Synchronous; HBX_ERR_STATE while batches are pending or after a failed
+ * submit; runs alone on the result stream; every stream is idle on return and
+ * the context stays usable after any failure.  n == 0 is HBX_OK with every
+ * link and root missing.  HBX_ERR_ARG, before anything is launched: a NULL
+ * context or summary; ids, n_links or link_base NULL with n > 0, links NULL
+ * with m > 0, root_ids NULL with n_roots > 0; n above 2^31 - 1; a row with
+ * link_base[i] + n_links[i] > m.  HBX_ERR_CAPACITY if the staging does not fit
+ * the free device memory.  Device memory, kept for the next call and freed by
+ * hbx_ctx_destroy, with S = hbx_idset_slots(n) table slots (8 to 16 bytes per
+ * row): 49 bytes per row (ID, count, base, flag, rep, two depths, two frontier
+ * words) + 4 S, 20 per link, 20 per root; with a faulty row 8 more per row
+ * and 4 per link of the sum of n_links (the transposed graph).
+ * Replaces the queue loop of MarkIndexes (gc.go:24-69) and the recursion of
+ * checkBlockFromIXEntry (integrity.go:298-329) over a table in memory. */
+int hbx_block_graph(hbx_ctx *ctx, uint64_t n, const uint8_t *ids, const uint32_t *n_links,
+                    const uint64_t *link_base, uint64_t m, const uint8_t *links, const uint8_t *bad,
+                    uint64_t n_roots, const uint8_t *root_ids, uint32_t *rep, uint32_t *link_row,
+                    uint32_t *root_row, uint32_t *mark_depth, uint32_t *fault_depth,
+                    hbx_graph_summary *summary);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
