@@ -6,7 +6,7 @@ the C-ABI in include/hbxgpu.h (libhbxgpu.so), with this package as the host
 mirror.  There is no CPU fallback in the product path.
 """
 from .engine import (ARENA_ALIGN, ARENA_SLACK, CONTENT_TYPE_FILE_CHAIN, CONTENT_TYPE_FILE_DATA,
-                     MAX_BLOCK_SIZE, MIN_BLOCK_SIZE, SEG_MIN_BYTES, SEG_OVERLAP, GRAPH_NONE, BlockGraph, ChainMatch, DatFileCheck, Engine, FileChunks, HbxError,
+                     MAX_BLOCK_SIZE, MIN_BLOCK_SIZE, SEG_MIN_BYTES, SEG_OVERLAP, GRAPH_NONE, BlockGraph, ChainMatch, CompactLimitError, DatCompact, DatFileCheck, Engine, FileChunks, HbxError,
                      IdSet, RestoredBlocks, RestoredFile, RestoredFiles, RestoreError, SegmentChunks, SegmentedFile, device_count, max_chunks, pack_arena_layout, plan_pipeline)
 from .shard import lpt_assign
 
@@ -14,4 +14,4 @@ __all__ = ["Engine", "FileChunks", "HbxError", "device_count", "max_chunks", "pa
            "lpt_assign", "plan_pipeline", "MIN_BLOCK_SIZE", "MAX_BLOCK_SIZE", "CONTENT_TYPE_FILE_DATA",
            "CONTENT_TYPE_FILE_CHAIN", "ARENA_ALIGN", "ARENA_SLACK", "SegmentedFile", "SEG_OVERLAP", "SEG_MIN_BYTES", "IdSet",
            "SegmentChunks", "RestoredBlocks", "RestoreError", "RestoredFile", "RestoredFiles", "ChainMatch", "DatFileCheck",
-           "BlockGraph", "GRAPH_NONE"]
+           "BlockGraph", "GRAPH_NONE", "DatCompact", "CompactLimitError"]

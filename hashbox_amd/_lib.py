@@ -47,6 +47,7 @@ EXPORTS = [
     "hbx_datfile_header_parse", "hbx_datfile_entry_parse", "hbx_datfile_walk",
     "hbx_datfile_check_device", "hbx_datfile_check_path", "hbx_datfile_verify_at",
     "hbx_block_graph",
+    "hbx_datfile_compact_plan", "hbx_datfile_compact_device", "hbx_datfile_compact_path",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -179,6 +180,25 @@ class GraphSummary(ctypes.Structure):
         "n_faulty", "n_invalid", "fault_levels", "n_marked_faulty")]
 
 
+class DatCompactArgs(ctypes.Structure):
+    """hbx_dat_compact_args: where a compaction's outputs will lie (K16)."""
+    _fields_ = [("file_no", ctypes.c_uint32), ("dst_file_no", ctypes.c_uint32), ("dst_base", ctypes.c_uint64),
+                ("meta_file_no", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("meta_base", ctypes.c_uint64)]
+
+
+class DatCompactSummary(ctypes.Structure):
+    """hbx_dat_compact_summary: what a compaction does to a data file (K16)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_entries", "n_stay", "n_moved", "n_dropped", "stay_end", "moved_bytes", "dropped_bytes", "deleted_bytes",
+        "meta_bytes", "n_meta", "first_past_limit")]
+
+
+CMP_DROP, CMP_STAY, CMP_MOVE = 0, 1, 2  # HBX_CMP_*
+CMP_F_KEEP_PREFIX = 1                   # HBX_CMP_F_KEEP_PREFIX
+DAT_OFFSET_LIMIT = (1 << 34) - 1        # HBX_DAT_OFFSET_LIMIT
+DAT_FILE_MAX = 0x3FFF                   # HBX_DAT_FILE_MAX
+IX_F_EXISTS, IX_F_NOLINKS = 1, 2        # HBX_IX_F_*
+META_HEAD, IX_ENTRY = 34, 24            # HBX_META_HEAD, HBX_IX_ENTRY
 GRAPH_NONE = 0xFFFFFFFF             # HBX_GRAPH_NONE
 GRAPH_LANE_MAX, GRAPH_WAVE_MAX = 16, 4096  # HBX_GRAPH_LANE_MAX, HBX_GRAPH_WAVE_MAX (hbx_knobs reports them)
 DAT_HEADER, DAT_IMAGE_SLACK = 16, 64            # HBX_DAT_HEADER, HBX_DAT_IMAGE_SLACK
@@ -334,6 +354,10 @@ def load() -> ctypes.CDLL:
                                          ctypes.POINTER(DatSummary)]
     L.hbx_datfile_verify_at.argtypes = [P, P, U64, ctypes.c_char_p, U64, P, P, I, U64, U64, P]
     L.hbx_block_graph.argtypes = [P, U64, P, P, P, U64, P, P, U64, P, P, P, P, P, P, ctypes.POINTER(GraphSummary)]
+    PCA, PCS = ctypes.POINTER(DatCompactArgs), ctypes.POINTER(DatCompactSummary)
+    L.hbx_datfile_compact_plan.argtypes = [U64, U64, P, P, PCA, P, P, P, PCS]
+    L.hbx_datfile_compact_device.argtypes = [P, P, U64, U64, P, P, PCA, P, P, P, P, U64, P, U64, P, U64, PCS]
+    L.hbx_datfile_compact_path.argtypes = [P, ctypes.c_char_p, U64, P, P, PCA, P, P, P, P, U64, P, U64, P, U64, PCS]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

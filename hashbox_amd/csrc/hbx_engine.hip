@@ -16,6 +16,7 @@
 #include <hsa/hsa_ext_amd.h>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cerrno>
@@ -47,9 +48,11 @@
 #include "hbx_restore_many.hip"
 #include "hbx_datfile.hip"
 #include "hbx_graph.hip"
+#include "hbx_compact.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 #include "hbx_datfile.h"
+#include "hbx_compact.h"
 
 namespace {
 
@@ -464,6 +467,9 @@ struct hbx_ctx {
   // hbx_block_graph (bg_layout names the buffers); K15's workgroup cap (0 = by size; HBX_K15_WGS: tests)
   DevBuf d_bg[16];
   uint32_t k15_wgs = 0;
+  // hbx_datfile_compact_* (the kCp* enum names the buffers); K16's tile in bytes (HBX_K16_TILE: tests)
+  DevBuf d_cp[12];
+  uint32_t k16_tile = hbxk::kTile;
   std::vector<hbx_seg*> segs_open;
   std::vector<DevBuf> seg_words;
   std::vector<uint64_t*> seg_words_free;
@@ -1906,6 +1912,8 @@ int hbx_ctx_create(int device, hbx_ctx** out) {
   if (const char* v = ab_env("HBX_K14_WGS")) c->k14_wgs = (uint32_t)std::min(65536, std::max(0, std::atoi(v)));
   // (tests: a K15 grid of one or two workgroups, so a small table spans several grid-stride rounds)
   if (const char* v = ab_env("HBX_K15_WGS")) c->k15_wgs = (uint32_t)std::min(65536, std::max(0, std::atoi(v)));
+  // (tests: K16 tiles of 256 and 4,096 bytes, so a small stream spans many tiles)
+  if (const char* v = ab_env("HBX_K16_TILE")) c->k16_tile = hbxk::tile_of(std::atoi(v));
   if (hipSetDevice(device) != hipSuccess || make_stream(&c->stream, "HBX_SCAN_CUS", ncu, "0:4096") != hipSuccess) {
     delete c;
     return HBX_ERR_HIP;
@@ -1985,6 +1993,7 @@ void hbx_ctx_destroy(hbx_ctx* c) {
   for (DevBuf& d : c->d_lc) d.release();
   for (DevBuf& d : c->d_df) d.release();
   for (DevBuf& d : c->d_bg) d.release();
+  for (DevBuf& d : c->d_cp) d.release();
   c->d_dfimg.release();
   for (PinBuf& h : c->h_dfstage) h.release();
   for (hbx_seg* h : c->segs_open) delete h;
@@ -2165,7 +2174,7 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       "\"sdma_d2h_mask\": %u, \"sdma_warm_ms\": %.3f, \"k3_spin\": %u, \"plan_addr\": %u, \"plan_addr_shift\": %u, \"k1_ext\": %u, \"k1_dma4\": %u, \"k1_early\": %u, "
       "\"restore_ms\": [%.3f, %.3f, %.3f, %.3f], \"restore_many\": [%llu, %llu, %llu], "
       "\"match_push_bytes\": %llu, \"k14_wgs\": %u, \"datfile\": [%llu, %llu], \"k15_wgs\": %u, "
-      "\"k15_lane_max\": %u, \"k15_wave_max\": %u}",
+      "\"k15_lane_max\": %u, \"k15_wave_max\": %u, \"k16_tile\": %u}",
       (ab && std::atoi(ab) != 0) ? 1 : 0, c->md5_slice, c->join_lag, c->tile_iters, c->k1_gate, c->md5_wgs,
       plan_mode_of(c), c->k2_own, c->k4_window, c->h_probe.p ? 1 : 0, c->lean_marks, c->k3_prod, c->k3_items,
       c->k3_period, c->meta_kernel, c->plan_cut, c->k1_swz, c->k3_psets, c->d2h_kernel,
@@ -2174,7 +2183,7 @@ int hbx_knobs(hbx_ctx* c, char* out, uint64_t cap) {
       c->restore_ms[0], c->restore_ms[1], c->restore_ms[2], c->restore_ms[3],
       (unsigned long long)c->many_windows, (unsigned long long)c->many_passes, (unsigned long long)c->many_retries,
       (unsigned long long)c->match_push_bytes, c->k14_wgs, (unsigned long long)c->dat_windows,
-      (unsigned long long)c->dat_retries, c->k15_wgs, hbxg::kLaneMax, hbxg::kWaveMax);
+      (unsigned long long)c->dat_retries, c->k15_wgs, hbxg::kLaneMax, hbxg::kWaveMax, c->k16_tile);
   return (n > 0 && (uint64_t)n < cap) ? HBX_OK : HBX_ERR_ARG;
 }
 
@@ -6384,9 +6393,226 @@ inline bool datfile_args_ok(const void* d_image, uint64_t max_block) {
   return (reinterpret_cast<uintptr_t>(d_image) & (HBX_ARENA_ALIGN - 1)) == 0 && restore_mb(max_block) <= kRestoreMaxBlock;
 }
 
+// ---- K16: compact a data file (DESIGN.md §5 "K16", hbx_compact.hip, hbx_compact.h) ----
+// hbx_ctx::d_cp
+enum { kCpEnt, kCpKeep, kCpKlass, kCpMsz, kCpTsz, kCpCnt, kCpMsrc, kCpMstart, kCpTot, kCpMoved, kCpMeta, kCpIx, kCpBufs };
+static_assert(kCpBufs == 12, "hbx_ctx::d_cp");
+
+struct CompactOut {
+  uint8_t* klass;
+  uint64_t *new_off, *meta_off;
+  uint8_t* moved;
+  uint64_t moved_cap;
+  uint8_t* meta;
+  uint64_t meta_cap;
+  uint8_t* ix;
+  uint64_t ix_cap;
+};
+
+inline bool compact_out_ok(const CompactOut& o) {
+  return !((o.moved_cap && !o.moved) || (o.meta_cap && !o.meta) || (o.ix_cap && !o.ix));
+}
+
+// Grow the named buffers of d_cp to need[], after checking the growth against the free device memory.
+int compact_fits(hbx_ctx* c, const size_t* need, std::initializer_list<int> which) {
+  uint64_t grow = 0;
+  for (int b : which)
+    if (need[b] > c->d_cp[b].cap) grow += need[b] + 4096 - c->d_cp[b].cap;
+  size_t fr = 0, tot = 0;
+  HBX_TRY(c, hipMemGetInfo(&fr, &tot));
+  if (grow > fr)
+    return c->fail(HBX_ERR_CAPACITY, "data file compaction needs " + std::to_string(grow) +
+                                         " more bytes of device memory, " + std::to_string(fr) + " are free");
+  for (int b : which) HBX_TRY(c, c->d_cp[b].ensure(need[b]));
+  return HBX_OK;
+}
+
+// The arguments are checked (hbxcmp::args_ok gave entry_bytes), n > 0, the context is locked and idle.
+int compact_run(hbx_ctx* c, const uint8_t* image, uint64_t size, uint64_t n, const hbx_dat_entry* ent,
+                const uint8_t* keep, const hbx_dat_compact_args* a, uint64_t entry_bytes, const CompactOut& o,
+                hbx_dat_compact_summary* sum) {
+  hipStream_t s = c->rstream;
+  // (targets of asynchronous copies: they outlive the body below, and a failure synchronises before they go)
+  unsigned long long tot[hbxk::kTotWords] = {};
+  uint8_t guard[4 * kImageGuard];
+  std::memset(guard, kGuardByte, sizeof guard);
+  const int rc = [&]() -> int {
+  const uint64_t chunks = (n + hbxg::kScanChunk - 1) / hbxg::kScanChunk;
+  size_t need[kCpBufs] = {};
+  need[kCpEnt] = n * sizeof(hbx_dat_entry);
+  need[kCpKeep] = need[kCpKlass] = n;
+  need[kCpMsz] = need[kCpTsz] = need[kCpCnt] = (n + chunks) * 8;
+  need[kCpMsrc] = need[kCpMstart] = (n + 1) * 8;
+  need[kCpTot] = hbxk::kTotWords * 8;
+  if (int rc = compact_fits(c, need, {kCpEnt, kCpKeep, kCpKlass, kCpMsz, kCpTsz, kCpCnt, kCpMsrc, kCpMstart, kCpTot}))
+    return rc;
+  unsigned long long* d_tot = c->d_cp[kCpTot].as<unsigned long long>();
+  unsigned long long* scans[3] = {c->d_cp[kCpMsz].as<unsigned long long>(), c->d_cp[kCpTsz].as<unsigned long long>(),
+                                  c->d_cp[kCpCnt].as<unsigned long long>()};
+  const hbxk::PlanArgs pa{c->d_cp[kCpEnt].as<hbx_dat_entry>(), c->d_cp[kCpKeep].as<uint8_t>(),
+                          c->d_cp[kCpKlass].as<uint8_t>(), scans[0], scans[1], scans[2],
+                          c->d_cp[kCpMsrc].as<unsigned long long>(), c->d_cp[kCpMstart].as<unsigned long long>(),
+                          d_tot, *a, (uint32_t)n};
+  const dim3 block(hbxk::kThreads), rows((uint32_t)((n + hbxk::kThreads - 1) / hbxk::kThreads));
+  // 1. the plan: the prefix break, class and sizes, three scans, the offsets and the movers' list
+  HBX_TRY(c, hipMemcpyAsync(c->d_cp[kCpEnt].p, ent, n * sizeof(hbx_dat_entry), hipMemcpyHostToDevice, s));
+  HBX_TRY(c, hipMemcpyAsync(c->d_cp[kCpKeep].p, keep, n, hipMemcpyHostToDevice, s));
+  HBX_TRY(c, hipMemsetAsync(d_tot, 0, hbxk::kTotWords * 8, s));
+  HBX_TRY(c, hipMemsetAsync(d_tot + hbxk::kTotPast, 0xFF, 8, s));
+  if (a->flags & HBX_CMP_F_KEEP_PREFIX) {
+    HBX_TRY(c, hipMemsetAsync(d_tot + hbxk::kTotBreak, 0xFF, 8, s));
+    hipLaunchKernelGGL(hbx_k16_break, rows, block, 0, s, pa);
+  }
+  hipLaunchKernelGGL(hbx_k16_plan, rows, block, 0, s, pa);
+  for (unsigned long long* x : scans) {
+    hipLaunchKernelGGL(hbx_k15_scan_sums, dim3((uint32_t)chunks), block, 0, s, x, n, x + n);
+    hipLaunchKernelGGL(hbx_k15_scan_top, dim3(1), block, 0, s, x + n, chunks);
+    hipLaunchKernelGGL(hbx_k15_scan_add, dim3((uint32_t)chunks), block, 0, s, x, n, x + n);
+  }
+  hipLaunchKernelGGL(hbx_k16_place, rows, block, 0, s, pa);
+  HBX_TRY(c, hipGetLastError());
+  HBX_TRY(c, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, s));
+  HBX_TRY(c, hipStreamSynchronize(s));
+  const uint64_t n_moved = tot[hbxk::kTotCounts] & 0xFFFFFFFFull, n_kept = tot[hbxk::kTotCounts] >> 32;
+  const uint64_t moved_bytes = tot[hbxk::kTotMoved], meta_bytes = tot[hbxk::kTotMeta];
+  if (n_moved > n_kept || n_kept > n || moved_bytes > entry_bytes)
+    return c->fail(HBX_ERR_STATE, "data file compaction: the device plan is inconsistent");
+  hbxcmp::summarize(size, n, ent, entry_bytes, n_kept - n_moved, n_moved, n_kept, moved_bytes, meta_bytes,
+                    tot[hbxk::kTotPast], sum);
+  auto plan_out = [&]() -> int {
+    if (o.klass) HBX_TRY(c, hipMemcpyAsync(o.klass, pa.klass, n, hipMemcpyDeviceToHost, s));
+    if (o.new_off) HBX_TRY(c, hipMemcpyAsync(o.new_off, pa.msz, n * 8, hipMemcpyDeviceToHost, s));
+    if (o.meta_off) HBX_TRY(c, hipMemcpyAsync(o.meta_off, pa.tsz, n * 8, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipStreamSynchronize(s));
+    return HBX_OK;
+  };
+  if (sum->first_past_limit != hbxcmp::kNever) {
+    if (int rc = plan_out()) return rc;
+    return c->fail(HBX_ERR_CAPACITY, "data file compaction: entry " + std::to_string(sum->first_past_limit) +
+                                         " would lie above the 16 GiB offset limit");
+  }
+  const uint64_t ix_bytes = HBX_IX_ENTRY * n_kept;
+  if ((o.moved && moved_bytes > o.moved_cap) || (o.meta && meta_bytes > o.meta_cap) || (o.ix && ix_bytes > o.ix_cap))
+    return c->fail(HBX_ERR_CAPACITY, "data file compaction: " + std::to_string(moved_bytes) + " moved, " +
+                                         std::to_string(meta_bytes) + " meta and " + std::to_string(ix_bytes) +
+                                         " index bytes do not fit the output capacities");
+  // 2. the streams, each between two guards
+  const bool want_moved = o.moved && moved_bytes, want_meta = o.meta && meta_bytes, want_ix = o.ix && ix_bytes;
+  need[kCpMoved] = want_moved ? moved_bytes + 2 * kImageGuard : 0;
+  need[kCpMeta] = want_meta ? meta_bytes + 2 * kImageGuard : 0;
+  need[kCpIx] = want_ix ? ix_bytes : 0;
+  if (int rc = compact_fits(c, need, {kCpMoved, kCpMeta, kCpIx})) return rc;
+  uint8_t* d_moved = want_moved ? c->d_cp[kCpMoved].as<uint8_t>() + kImageGuard : nullptr;
+  uint8_t* d_meta = want_meta ? c->d_cp[kCpMeta].as<uint8_t>() + kImageGuard : nullptr;
+  if (want_moved) {
+    const uint64_t tiles = (moved_bytes + c->k16_tile - 1) / c->k16_tile;
+    if (tiles > 0x7FFFFFFFull) return c->fail(HBX_ERR_ARG, "data file compaction: too many tiles");
+    HBX_TRY(c, hipMemsetAsync(d_moved - kImageGuard, kGuardByte, kImageGuard, s));
+    HBX_TRY(c, hipMemsetAsync(d_moved + moved_bytes, kGuardByte, kImageGuard, s));
+    const hbxk::PackArgs ka{image, pa.msrc, pa.mstart, d_moved, moved_bytes, (uint32_t)n_moved, c->k16_tile};
+    hipLaunchKernelGGL(hbx_k16_pack, dim3((uint32_t)tiles), block, 0, s, ka);
+    HBX_TRY(c, hipGetLastError());
+    HBX_TRY(c, hipMemcpyAsync(guard, d_moved - kImageGuard, kImageGuard, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipMemcpyAsync(guard + kImageGuard, d_moved + moved_bytes, kImageGuard, hipMemcpyDeviceToHost, s));
+    HBX_TRY(c, hipMemcpyAsync(o.moved, d_moved, moved_bytes, hipMemcpyDeviceToHost, s));
+  }
+  if (want_meta || want_ix) {
+    if (want_meta) {
+      HBX_TRY(c, hipMemsetAsync(d_meta - kImageGuard, kGuardByte, kImageGuard, s));
+      HBX_TRY(c, hipMemsetAsync(d_meta + meta_bytes, kGuardByte, kImageGuard, s));
+    }
+    const hbxk::MetaArgs ma{image, pa.ent, pa.klass, pa.msz, pa.tsz, pa.cnt, d_meta,
+                            want_ix ? c->d_cp[kCpIx].as<uint8_t>() : nullptr, *a, (uint32_t)n};
+    hipLaunchKernelGGL(hbx_k16_meta, dim3(hbxg::grid(n, 0)), block, 0, s, ma);
+    HBX_TRY(c, hipGetLastError());
+    if (want_meta) {
+      HBX_TRY(c, hipMemcpyAsync(guard + 2 * kImageGuard, d_meta - kImageGuard, kImageGuard, hipMemcpyDeviceToHost, s));
+      HBX_TRY(c, hipMemcpyAsync(guard + 3 * kImageGuard, d_meta + meta_bytes, kImageGuard, hipMemcpyDeviceToHost, s));
+      HBX_TRY(c, hipMemcpyAsync(o.meta, d_meta, meta_bytes, hipMemcpyDeviceToHost, s));
+    }
+    if (want_ix) HBX_TRY(c, hipMemcpyAsync(o.ix, c->d_cp[kCpIx].p, ix_bytes, hipMemcpyDeviceToHost, s));
+  }
+  if (int rc = plan_out()) return rc;
+  for (uint8_t b : guard)
+    if (b != kGuardByte) return c->fail(HBX_ERR_STATE, "data file compaction: K16 wrote outside a stream");
+  return HBX_OK;
+  }();
+  if (rc != HBX_OK) {
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
+// Both entry points behind their argument checks: `path` or `d_image`.
+int compact_call(hbx_ctx* c, const char* path, const void* d_image, uint64_t size, uint64_t n,
+                 const hbx_dat_entry* ent, const uint8_t* keep, const hbx_dat_compact_args* a, const CompactOut& o,
+                 hbx_dat_compact_summary* sum) {
+  std::lock_guard<std::mutex> g(c->mu);
+  if (!c->pending.empty()) return c->fail(HBX_ERR_STATE, "submitted batches are still pending");
+  if (c->broken) return c->fail(HBX_ERR_STATE, "context is unusable after a failed submit; destroy it");
+  HBX_TRY(c, hipSetDevice(c->device));
+  const uint8_t* image = static_cast<const uint8_t*>(d_image);
+  uint64_t entry_bytes = 0;
+  if (path) {  // (only the file tells its size: the entries are checked against it before anything is launched)
+    struct stat st;
+    if (::stat(path, &st) != 0) return c->fail(HBX_ERR_IO, std::string("cannot open ") + path + ": " + std::strerror(errno));
+    size = (uint64_t)st.st_size;
+  }
+  if (!hbxcmp::args_ok(size, n, ent, keep, a, &entry_bytes))
+    return c->fail(HBX_ERR_ARG, "data file compaction: the entries do not ascend inside a file of " + std::to_string(size) +
+                                    " bytes, a size is not 29 + 16 n_links + data_len or is above 2^32 - 1, or a file "
+                                    "number or a base is out of range");
+  if (n == 0) {
+    hbxcmp::summarize(size, 0, ent, 0, 0, 0, 0, 0, 0, hbxcmp::kNever, sum);
+    return HBX_OK;
+  }
+  int rc = HBX_OK;
+  if (path) {
+    uint64_t loaded = 0;
+    rc = datfile_load(c, path, &image, &loaded);
+    if (rc == HBX_OK && loaded != size) rc = c->fail(HBX_ERR_IO, std::string(path) + " changed its size while it was read");
+  }
+  if (rc == HBX_OK) rc = compact_run(c, image, size, n, ent, keep, a, entry_bytes, o, sum);
+  if (rc != HBX_OK) {  // leave the streams idle and the error state clean: the context stays usable
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->rstream);
+    (void)hipGetLastError();
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hbx_datfile_compact_plan(uint64_t size, uint64_t n, const hbx_dat_entry* entries, const uint8_t* keep,
+                             const hbx_dat_compact_args* args, uint8_t* klass, uint64_t* new_off, uint64_t* meta_off,
+                             hbx_dat_compact_summary* summary) {
+  return hbxcmp::plan(size, n, entries, keep, args, klass, new_off, meta_off, summary);
+}
+
+int hbx_datfile_compact_device(hbx_ctx* c, const void* d_image, uint64_t size, uint64_t n,
+                               const hbx_dat_entry* entries, const uint8_t* keep, const hbx_dat_compact_args* args,
+                               uint8_t* klass, uint64_t* new_off, uint64_t* meta_off, uint8_t* moved_out,
+                               uint64_t moved_cap, uint8_t* meta_out, uint64_t meta_cap, uint8_t* ix_out,
+                               uint64_t ix_cap, hbx_dat_compact_summary* summary) {
+  const CompactOut o{klass, new_off, meta_off, moved_out, moved_cap, meta_out, meta_cap, ix_out, ix_cap};
+  if (!c || !d_image || !summary || !args || !compact_out_ok(o) ||
+      (reinterpret_cast<uintptr_t>(d_image) & (HBX_ARENA_ALIGN - 1)) != 0)
+    return HBX_ERR_ARG;
+  return compact_call(c, nullptr, d_image, size, n, entries, keep, args, o, summary);
+}
+
+int hbx_datfile_compact_path(hbx_ctx* c, const char* path, uint64_t n, const hbx_dat_entry* entries,
+                             const uint8_t* keep, const hbx_dat_compact_args* args, uint8_t* klass,
+                             uint64_t* new_off, uint64_t* meta_off, uint8_t* moved_out, uint64_t moved_cap,
+                             uint8_t* meta_out, uint64_t meta_cap, uint8_t* ix_out, uint64_t ix_cap,
+                             hbx_dat_compact_summary* summary) {
+  const CompactOut o{klass, new_off, meta_off, moved_out, moved_cap, meta_out, meta_cap, ix_out, ix_cap};
+  if (!c || !path || !summary || !args || !compact_out_ok(o)) return HBX_ERR_ARG;
+  return compact_call(c, path, nullptr, 0, n, entries, keep, args, o, summary);
+}
 
 int hbx_datfile_header_parse(const uint8_t* in, uint64_t len, uint32_t* filetype, uint32_t* version,
                              uint64_t* deadspace) {

@@ -94,6 +94,18 @@ DAT_ENTRY_DTYPE = np.dtype([("off", np.uint64), ("size", np.uint64), ("data_off"
                             ("type", np.uint8), ("id", np.uint8, (16,))])
 DAT_SPAN_DTYPE = np.dtype([("off", np.uint64), ("len", np.uint64), ("kind", np.uint32), ("status", np.uint32),
                            ("n_failed", np.uint64)])
+# the same fields where hbx_dat_entry has them (64 bytes): what a call that takes entries is given
+_DAT_ENTRY_C = np.dtype({"names": list(DAT_ENTRY_DTYPE.names),
+                         "formats": [DAT_ENTRY_DTYPE[k] for k in DAT_ENTRY_DTYPE.names],
+                         "offsets": [0, 8, 16, 24, 32, 36, 40, 44, 48], "itemsize": 64})
+
+
+def _c_entries(entries) -> np.ndarray:
+    e = np.asarray(entries)
+    out = np.zeros(e.shape[0], _DAT_ENTRY_C)
+    for name in DAT_ENTRY_DTYPE.names:
+        out[name] = e[name]
+    return out
 
 
 @dataclass(slots=True)
@@ -105,6 +117,51 @@ class DatFileCheck:
     spans: np.ndarray  # DAT_SPAN_DTYPE [n_spans]: gaps (kind 0) and broken spans (kind 1), ascending
     summary: dict  # hbx_dat_summary's fields; truncate_at is None when the walk did not end in damage
     links: Optional[np.ndarray]  # uint8 [summary["n_links"], 16]: entry e's are links[link_base : link_base + n_links]
+
+
+@dataclass(slots=True)
+class DatCompact:
+    """What :meth:`Engine.compact_datfile` returns (hbx_datfile_compact_*):
+    what CompactFile (pkg/storagedb/gc.go:208-318) would do to a data file, as
+    bytes.  Nothing is written anywhere."""
+    entries: np.ndarray  # DAT_ENTRY_DTYPE [n]: the table the call was given
+    klass: np.ndarray  # uint8 [n]: 0 dropped, 1 stays where it is, 2 moved
+    new_off: np.ndarray  # uint64 [n]: where the entry lies afterwards (a dropped one: 2^64 - 1)
+    meta_off: np.ndarray  # uint64 [n]: where its meta record lies (a dropped one: 2^64 - 1)
+    moved: Optional[bytes]  # the moved entries back to back: what is appended at dst_base
+    meta: Optional[bytes]  # one StorageMetaEntry per kept entry: what is appended at meta_base
+    ix: Optional[np.ndarray]  # uint8 [n_meta, 24]: one StorageIXEntry per kept entry
+    summary: dict  # hbx_dat_compact_summary's fields; first_past_limit is None when nothing passes the limit
+    file_no: int
+    dst_file_no: int
+
+    @property
+    def stay(self) -> np.ndarray:
+        return self.klass == _lib.CMP_STAY
+
+    @property
+    def moved_rows(self) -> np.ndarray:
+        return self.klass == _lib.CMP_MOVE
+
+    @property
+    def relocations(self) -> list:
+        """(id, file, offset) of every moved entry: changeDataLocation's arguments (gc.go:284, 303)."""
+        return [(self.entries["id"][i].tobytes(), self.dst_file_no, int(self.new_off[i]))
+                for i in np.flatnonzero(self.moved_rows)]
+
+
+class CompactLimitError(HbxError):
+    """:meth:`Engine.compact_datfile`: an offset would lie above the 16 GiB
+    limit of a location (HBX_ERR_CAPACITY with ``first_past_limit``).
+    ``plan`` is the :class:`DatCompact` of the call without streams (``moved``,
+    ``meta`` and ``ix`` are None): its ``klass``, ``new_off``, ``meta_off`` and
+    ``summary`` are complete, so the caller can cut the list at
+    ``first_past_limit`` and call again with the next file as destination."""
+
+    def __init__(self, msg: str, plan: "DatCompact"):
+        super().__init__(msg)
+        self.plan = plan
+        self.first_past_limit = plan.summary["first_past_limit"]
 
 
 GRAPH_NONE = _lib.GRAPH_NONE
@@ -770,6 +827,81 @@ class Engine:
             if arena is not None:
                 self._L.hbx_arena_free(self._ctx, arena)
         return st[:n]
+
+    def compact_datfile(self, source, entries, keep, file_no: int = 0, dst_file_no: Optional[int] = None,
+                        dst_base: int = 16, keep_prefix: bool = True, meta_file_no: int = 0, meta_base: int = 16,
+                        moved: bool = True, meta: bool = True, ix: bool = True,
+                        size: Optional[int] = None) -> DatCompact:
+        """Compact a storage data file on the device (K16; hbx_datfile_compact_path
+        / _device): CompactFile (pkg/storagedb/gc.go:208-318) over the file's
+        image, as bytes.  ``entries`` are :meth:`check_datfile`'s, ``keep`` one
+        flag each (:func:`formats.gc_keep` makes them from a block graph).  The
+        kept entries at the start of the file stay (``keep_prefix``); every other
+        kept entry is packed into ``moved``, which the caller appends to data
+        file ``dst_file_no`` (None: ``file_no``) at ``dst_base``; ``meta`` holds
+        one StorageMetaEntry per kept entry for ``meta_file_no`` at ``meta_base``
+        and ``ix`` their StorageIXEntry records.  ``source`` as
+        :meth:`check_datfile`.  Nothing is written or truncated.  The buffers
+        are sized from a first guess and, when the library reports larger
+        sizes, from those (the call then runs once more).  An offset above the
+        16 GiB limit of a location raises :class:`CompactLimitError`, which
+        carries the complete plan."""
+        ent = _c_entries(entries)
+        n = int(ent.shape[0])
+        kp = np.ascontiguousarray(np.asarray(keep).reshape(-1) != 0, np.uint8)
+        if kp.shape[0] != n:
+            raise ValueError("one keep flag per entry")
+        dst = file_no if dst_file_no is None else dst_file_no
+        args = _lib.DatCompactArgs(int(file_no), int(dst), int(dst_base), int(meta_file_no),
+                                   _lib.CMP_F_KEEP_PREFIX if keep_prefix else 0, int(meta_base))
+        klass, new_off, meta_off = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64)
+        sm = _lib.DatCompactSummary()
+        # (what the streams take if every kept entry moves; the library says if a table needs more)
+        kept = kp != 0
+        caps = [int(ent["size"][kept].sum()) if moved else 0,
+                int((_lib.META_HEAD + 16 * ent["n_links"][kept].astype(np.uint64)).sum()) if meta else 0,
+                _lib.IX_ENTRY * int(kept.sum()) if ix else 0]
+        d, sz, path, arena = self._dat_image(source, size)
+        try:
+            for _ in range(2):
+                bufs = [np.zeros(max(c, 1), np.uint8) for c in caps]
+                outs = []
+                for want, b, c in zip((moved, meta, ix), bufs, caps):
+                    outs += [_p(b) if want else None, c]
+                tail = (n, _p(ent), _p(kp), ctypes.byref(args), _p(klass), _p(new_off), _p(meta_off), *outs,
+                        ctypes.byref(sm))
+                if path is not None:
+                    rc = self._L.hbx_datfile_compact_path(self._ctx, path, *tail)
+                else:
+                    rc = self._L.hbx_datfile_compact_device(self._ctx, d, sz, *tail)
+                need = [int(sm.moved_bytes), int(sm.meta_bytes), _lib.IX_ENTRY * int(sm.n_meta)]
+                if rc != _lib.ERR_CAPACITY or sm.first_past_limit != _lib.NO_DIFF or \
+                        not any(w and x > c for w, x, c in zip((moved, meta, ix), need, caps)):
+                    break
+                caps = [max(c, x) if w else 0 for w, x, c in zip((moved, meta, ix), need, caps)]
+            past = rc == _lib.ERR_CAPACITY and sm.first_past_limit != _lib.NO_DIFF
+            if not past:
+                self._check(rc, "hbx_datfile_compact")
+            else:
+                msg = self._L.hbx_last_error(self._ctx)
+        finally:
+            if arena is not None:
+                self._L.hbx_arena_free(self._ctx, arena)
+        summary = {k: int(getattr(sm, k)) for k, _ in _lib.DatCompactSummary._fields_}
+        if summary["first_past_limit"] == _lib.NO_DIFF:
+            summary["first_past_limit"] = None
+        e = np.zeros(n, DAT_ENTRY_DTYPE)
+        for name in DAT_ENTRY_DTYPE.names:
+            e[name] = ent[name]
+        if past:  # the plan is complete and nothing was packed: hand it to the caller with the error
+            raise CompactLimitError(f"hbx_datfile_compact: HBX_ERR_CAPACITY: {msg.decode() if msg else ''}",
+                                    DatCompact(e, klass[:n], new_off[:n], meta_off[:n], None, None, None, summary,
+                                               int(file_no), int(dst)))
+        return DatCompact(e, klass[:n], new_off[:n], meta_off[:n],
+                          bufs[0][:need[0]].tobytes() if moved else None,
+                          bufs[1][:need[1]].tobytes() if meta else None,
+                          bufs[2][:need[2]].reshape(-1, _lib.IX_ENTRY).copy() if ix else None,
+                          summary, int(file_no), int(dst))
 
     def match_paths(self, paths: Sequence[Union[str, os.PathLike]], chains_ids, io_threads: int = 16,
                     batch_bytes: int = 1 << 30, sizes: Optional[Sequence[int]] = None,

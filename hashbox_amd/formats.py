@@ -351,6 +351,26 @@ def block_table(checks) -> tuple:
             cat(fno, np.uint32), cat(off, np.uint64))
 
 
+def gc_keep(graph, file_no, force: bool = False) -> list:
+    """The sweep's verdict per data file for :meth:`Engine.compact_datfile`:
+    ``graph`` is the :class:`BlockGraph` of a :func:`block_table` and
+    ``file_no`` that table's fifth array.  Returns one bool array per data
+    file (file 0 first; a file without rows gets an empty one), True where the
+    row is marked and is its ID's representative: what the roots reach, once
+    per ID (``graph.marked & ~graph.alias``).  Raises if a marked tree is
+    damaged (``n_marked_faulty``): sweeping then would delete what a repair
+    still needs; ``force`` sweeps anyway."""
+    if graph.summary["n_marked_faulty"] and not force:
+        raise ValueError(f"{graph.summary['n_marked_faulty']} marked blocks have a damaged tree below them: "
+                         "repair first, or pass force=True")
+    fno = np.asarray(file_no).reshape(-1)
+    live = np.asarray(graph.marked) & ~np.asarray(graph.alias)
+    if fno.shape[0] != live.shape[0]:
+        raise ValueError("one file number per row of the graph")
+    n_files = int(fno.max()) + 1 if fno.shape[0] else 0
+    return [live[fno == f] for f in range(n_files)]
+
+
 def _read_verified(eng: Engine, read_block, block_id: bytes, what: str) -> bytes:
     """ReadBlock + VerifyBlock of one directory or chain block: its data,
     inflated and hashed with its links on the device (Engine.restore_blocks)."""

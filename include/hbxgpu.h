@@ -1271,6 +1271,128 @@ int hbx_block_graph(hbx_ctx *ctx, uint64_t n, const uint8_t *ids, const uint32_t
                     uint32_t *root_row, uint32_t *mark_depth, uint32_t *fault_depth,
                     hbx_graph_summary *summary);
 
+/* ---- Compact a storage data file: pack, relocate, meta (K16) -----------------------
+ * hbx_datfile_check_* gives a data file's good entries, hbx_block_graph which
+ * of a store's rows the roots reach.  The server's next step is CompactFile
+ * (pkg/storagedb/gc.go:208-318): it reads the file one entry at a time, drops
+ * what no index entry points at, leaves the kept entries at the file's start
+ * where they are, appends every other kept entry to the store's free file and
+ * changes its location (changeDataLocation), and truncates the file at the
+ * high-water mark.  These calls do that over one file image on the device
+ * (K16, hbx_compact.hip) and also build the StorageMetaEntry (meta.go:21-39)
+ * and the StorageIXEntry (index.go:24-38) each kept entry then needs.  They
+ * report and return bytes; they open no store file for writing.
+ *
+ * Input: the image of `size` bytes (hbx_datfile_check_device's rules: 16-byte
+ * aligned, HBX_DAT_IMAGE_SLACK readable bytes behind it), entries[n] as
+ * hbx_datfile_check_* returns them (ascending, not overlapping), keep[n]
+ * (non-zero: readIXEntry succeeds and VerifyLocation is true, gc.go:258-264)
+ * and *args.
+ *  1. Class.  klass[i] is HBX_CMP_DROP where keep[i] == 0; HBX_CMP_STAY where
+ *     HBX_CMP_F_KEEP_PREFIX is set, every entry j <= i is kept and
+ *     off[i] == 16 + sum of size[j] over j < i (the reference's readOffset ==
+ *     highWaterMark with freeFileNum >= fileNumber, gc.go:266-268: a gap, a
+ *     broken span or a dropped entry in front ends the prefix for good);
+ *     HBX_CMP_MOVE for every other kept entry.  stay_end = 16 + the stayers'
+ *     bytes: the reference's highWaterMark, where the source file is truncated.
+ *  2. Moved stream.  The movers' bytes verbatim, in file order, back to back.
+ *     new_off[i] = dst_base + the sizes of the movers before i; a stayer's
+ *     new_off is its off, a dropped entry's UINT64_MAX.
+ *  3. Meta stream.  One StorageMetaEntry per kept entry, in order, back to back
+ *     from meta_base: "hblk" | id[16] | location[6] | BE32 DataSize | BE32
+ *     n_links | links (34 + 16 n_links bytes).  location is sixByteLocation(file,
+ *     new_off), the 48-bit big-endian file << 34 | off (storagedb.go:90-101),
+ *     file = file_no for a stayer and dst_file_no for a mover; DataSize is the
+ *     entry's size; the links are copied from the image at off + 24.
+ *     meta_off[i] is where entry i's record starts (meta_base + the record
+ *     sizes of the kept entries before i); a dropped entry's is UINT64_MAX.
+ *  4. Index records.  One 24-byte StorageIXEntry per kept entry, in order, as
+ *     a flat array: BE16 flags | id | sixByteLocation(meta_file_no, meta_off[i]);
+ *     flags is HBX_IX_F_EXISTS, with HBX_IX_F_NOLINKS when n_links == 0
+ *     (data.go:96-100).  Placing them in the open-addressed index files stays
+ *     with the caller.
+ *  5. Summary: the counts and bytes per class; deleted_bytes = size - 16 - the
+ *     stayers' bytes - moved_bytes (the reference's `deleted` on a file without
+ *     broken spans; 0 for size < 16).
+ *  6. A location holds 34 bits of offset.  If a stayer's or a mover's new_off
+ *     or a meta_off would lie above HBX_DAT_OFFSET_LIMIT the call returns
+ *     HBX_ERR_CAPACITY: the summary is complete, first_past_limit is the first
+ *     such entry, klass / new_off / meta_off are written and nothing is
+ *     packed.  The caller cuts the list there and calls again with the next
+ *     file as destination.  Otherwise first_past_limit is UINT64_MAX.
+ *  7. Where the reference aborts on a damaged file (Unserialize panics), the
+ *     entry list is the authority here: whatever it does not name is deleted.
+ *     The free-space check (gc.go:269) and the index updates are the caller's.
+ *  8. HBX_ERR_ARG, before anything is launched: a NULL context, image, args
+ *     or summary, an unaligned image; entries or keep NULL with n > 0, n above
+ *     2^31 - 1; entries that do not ascend, that overlap, that start below 16
+ *     or end past size; size != 29 + 16 n_links + data_len, or a size above
+ *     2^32 - 1 (DataSize is a uint32); a file number above
+ *     0x3fff; dst_base or meta_base below 16 (or so large that an offset
+ *     leaves 64 bits); an output NULL with a capacity.
+ * Any output may be NULL with capacity 0: not wanted, and a stream nobody wants
+ * is not built.  n == 0 is HBX_OK. */
+#define HBX_DAT_OFFSET_LIMIT 0x3FFFFFFFFull /* 2^34 - 1: storageOffsetLimit (storagedb.go:52) */
+#define HBX_DAT_FILE_MAX 0x3FFFu
+#define HBX_CMP_DROP 0u
+#define HBX_CMP_STAY 1u
+#define HBX_CMP_MOVE 2u
+#define HBX_CMP_F_KEEP_PREFIX 1u
+#define HBX_IX_F_EXISTS 1u  /* entryFlagExists (storagedb.go:56) */
+#define HBX_IX_F_NOLINKS 2u /* entryFlagNoLinks */
+#define HBX_META_HEAD 34u   /* a StorageMetaEntry without links */
+#define HBX_IX_ENTRY 24u    /* storageIXEntrySize */
+typedef struct {
+  uint32_t file_no;      /* the file compacted: a stayer's location */
+  uint32_t dst_file_no;  /* the file the moved stream is appended to ... */
+  uint64_t dst_base;     /* ... at this offset */
+  uint32_t meta_file_no; /* the meta file the meta stream is appended to ... */
+  uint32_t flags;        /* HBX_CMP_F_* */
+  uint64_t meta_base;    /* ... at this offset */
+} hbx_dat_compact_args;  /* 32 bytes */
+typedef struct {
+  uint64_t n_entries, n_stay, n_moved, n_dropped;
+  uint64_t stay_end, moved_bytes, dropped_bytes, deleted_bytes;
+  uint64_t meta_bytes, n_meta; /* n_meta = n_stay + n_moved: meta records, and index records */
+  uint64_t first_past_limit;
+} hbx_dat_compact_summary;     /* 88 bytes */
+/* Rules 1-6 and 8 on the host (no context, no device), exactly as the device
+ * applies them: klass [n] (uint8), new_off [n], meta_off [n] (each may be
+ * NULL) and *summary.  HBX_OK, HBX_ERR_ARG (rule 8; `size` is the file's) or
+ * HBX_ERR_CAPACITY (rule 6). */
+int hbx_datfile_compact_plan(uint64_t size, uint64_t n, const hbx_dat_entry *entries, const uint8_t *keep,
+                             const hbx_dat_compact_args *args, uint8_t *klass, uint64_t *new_off,
+                             uint64_t *meta_off, hbx_dat_compact_summary *summary);
+/* The whole of it for the image at d_image (device memory); every other pointer
+ * is host memory.  moved_out (moved_cap bytes), meta_out (meta_cap bytes) and
+ * ix_out (ix_cap bytes, 24 per kept entry) receive the three outputs.
+ * HBX_ERR_CAPACITY if a wanted output's capacity is too small: the summary
+ * then holds the needed sizes (moved_bytes, meta_bytes, 24 n_meta) and no
+ * array is written.  Synchronous; HBX_ERR_STATE while batches are pending or
+ * after a failed submit; runs alone on the result stream; every stream is idle
+ * on return and the context stays usable after any failure; no part of a batch.
+ * Device memory beside the image is checked against the free memory first
+ * (HBX_ERR_CAPACITY), kept for the next call and freed by hbx_ctx_destroy: 106
+ * bytes per entry (the table 64, keep and class 2, three scans 24, the movers'
+ * list 16) + the wanted outputs + 128 guard bytes per stream.  Both packed streams lie between 64 guard bytes that hold
+ * a pattern during the call and are checked after it (HBX_ERR_STATE on a
+ * mismatch), as K10's and K11's images.  The device plan equals
+ * hbx_datfile_compact_plan word for word. */
+int hbx_datfile_compact_device(hbx_ctx *ctx, const void *d_image, uint64_t size, uint64_t n,
+                               const hbx_dat_entry *entries, const uint8_t *keep,
+                               const hbx_dat_compact_args *args, uint8_t *klass, uint64_t *new_off,
+                               uint64_t *meta_off, uint8_t *moved_out, uint64_t moved_cap, uint8_t *meta_out,
+                               uint64_t meta_cap, uint8_t *ix_out, uint64_t ix_cap,
+                               hbx_dat_compact_summary *summary);
+/* The same for the file at `path`, read through hbx_datfile_check_path's
+ * reader into the kept device image (HBX_ERR_IO, HBX_ERR_CAPACITY as there);
+ * `size` in rule 8 is the file's. */
+int hbx_datfile_compact_path(hbx_ctx *ctx, const char *path, uint64_t n, const hbx_dat_entry *entries,
+                             const uint8_t *keep, const hbx_dat_compact_args *args, uint8_t *klass,
+                             uint64_t *new_off, uint64_t *meta_off, uint8_t *moved_out, uint64_t moved_cap,
+                             uint8_t *meta_out, uint64_t meta_cap, uint8_t *ix_out, uint64_t ix_cap,
+                             hbx_dat_compact_summary *summary);
+
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
 int hbx_arena_free(hbx_ctx *ctx, void *d_ptr);
