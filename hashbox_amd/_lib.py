@@ -48,6 +48,10 @@ EXPORTS = [
     "hbx_datfile_check_device", "hbx_datfile_check_path", "hbx_datfile_verify_at",
     "hbx_block_graph",
     "hbx_datfile_compact_plan", "hbx_datfile_compact_device", "hbx_datfile_compact_path",
+    "hbx_index_open", "hbx_index_open_paths", "hbx_index_close", "hbx_index_sizes", "hbx_index_export",
+    "hbx_index_lookup", "hbx_index_scan", "hbx_index_mark", "hbx_index_update", "hbx_index_sweep",
+    "hbx_index_compact", "hbx_index_lookup_host", "hbx_index_scan_host", "hbx_index_mark_host",
+    "hbx_index_update_host", "hbx_index_sweep_host", "hbx_index_compact_host",
 ]
 # Functions returning something other than an int status.
 _NON_STATUS = ("hbx_ctx_destroy", "hbx_last_error", "hbx_max_chunks", "hbx_file_entry_size",
@@ -193,11 +197,45 @@ class DatCompactSummary(ctypes.Structure):
         "meta_bytes", "n_meta", "first_past_limit")]
 
 
+IX_FILES_MAX = 16  # HBX_IX_FILES_MAX
+
+
+class IxFileStats(ctypes.Structure):
+    """hbx_ix_file_stats: what a scan of one index file found (K17)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "slots", "n_live", "n_invalid", "n_empty", "n_marked", "n_nolinks", "n_misplaced", "first_misplaced",
+        "trunc_point")]
+
+
+class IxSummary(ctypes.Structure):
+    """hbx_ix_summary: a scan's counts over all index files (K17)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_files", "slots", "n_live", "n_invalid", "n_empty", "n_marked", "n_nolinks", "n_misplaced", "n_obsolete",
+        "n_cut_off")]
+
+
+class IxSweepSummary(ctypes.Structure):
+    """hbx_ix_sweep_summary: what SweepIndexes did (K17)."""
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n_live", "n_deleted", "n_stay", "n_obsolete", "n_moved", "n_abort", "first_abort", "swept_records",
+        "n_grown")]
+
+
+class IxCompactSummary(ctypes.Structure):
+    """hbx_ix_compact_summary: what CompactIndexes did (K17)."""
+    _fields_ = [("n_files", ctypes.c_uint64), ("cleared", ctypes.c_uint64), ("size", ctypes.c_uint64 * IX_FILES_MAX)]
+
+
 CMP_DROP, CMP_STAY, CMP_MOVE = 0, 1, 2  # HBX_CMP_*
 CMP_F_KEEP_PREFIX = 1                   # HBX_CMP_F_KEEP_PREFIX
 DAT_OFFSET_LIMIT = (1 << 34) - 1        # HBX_DAT_OFFSET_LIMIT
 DAT_FILE_MAX = 0x3FFF                   # HBX_DAT_FILE_MAX
 IX_F_EXISTS, IX_F_NOLINKS = 1, 2        # HBX_IX_F_*
+IX_F_MARKED, IX_F_INVALID = 4, 8        # HBX_IX_F_*
+IX_HEADER, IX_PROBE_LIMIT = 16, 682     # HBX_IX_HEADER, HBX_IX_PROBE_LIMIT
+IX_SLOTS_MAX = (1 << 24) + 682          # HBX_IX_SLOTS_MAX
+IX_SWEEP_TILE = 256                     # HBX_IX_SWEEP_TILE
+IX_ACT_DELETED, IX_ACT_STAY, IX_ACT_OBSOLETE, IX_ACT_MOVED, IX_ACT_ABORT = 1, 2, 3, 4, 5  # HBX_IX_ACT_*
 META_HEAD, IX_ENTRY = 34, 24            # HBX_META_HEAD, HBX_IX_ENTRY
 GRAPH_NONE = 0xFFFFFFFF             # HBX_GRAPH_NONE
 GRAPH_LANE_MAX, GRAPH_WAVE_MAX = 16, 4096  # HBX_GRAPH_LANE_MAX, HBX_GRAPH_WAVE_MAX (hbx_knobs reports them)
@@ -210,6 +248,7 @@ BLOCK_RAW, BLOCK_ZLIB = 0xFF, 0x01  # HBX_BLOCK_RAW, HBX_BLOCK_ZLIB
 MAX_BLOCK = 8 << 20                 # HBX_MAX_BLOCK
 ERR_IO, ERR_VERIFY = -4, -9
 ERR_CAPACITY = -3
+ERR_ARG, ERR_STATE, ERR_FORMAT = -1, -6, -7
 NO_DIFF = (1 << 64) - 1             # first_diff when nothing differs
 
 _lib = None
@@ -358,6 +397,25 @@ def load() -> ctypes.CDLL:
     L.hbx_datfile_compact_plan.argtypes = [U64, U64, P, P, PCA, P, P, P, PCS]
     L.hbx_datfile_compact_device.argtypes = [P, P, U64, U64, P, P, PCA, P, P, P, P, U64, P, U64, P, U64, PCS]
     L.hbx_datfile_compact_path.argtypes = [P, ctypes.c_char_p, U64, P, P, PCA, P, P, P, P, U64, P, U64, P, U64, PCS]
+    U32 = ctypes.c_uint32
+    L.hbx_index_open.argtypes = [P, U32, P, P, ctypes.POINTER(P)]
+    L.hbx_index_open_paths.argtypes = [P, U32, P, ctypes.POINTER(P)]
+    L.hbx_index_close.argtypes = [P, P]
+    L.hbx_index_sizes.argtypes = [P, P, P]
+    L.hbx_index_export.argtypes = [P, P, U32, P, U64, PU64]
+    L.hbx_index_lookup.argtypes = [P, P, U64, P, I, P]
+    L.hbx_index_scan.argtypes = [P, P, P, U64, P, ctypes.POINTER(IxSummary)]
+    L.hbx_index_mark.argtypes = [P, P, U64, P, P, PU64]
+    L.hbx_index_update.argtypes = [P, P, U64, P, P]
+    L.hbx_index_sweep.argtypes = [P, P, P, P, U64, P, U64, ctypes.POINTER(IxSweepSummary)]
+    L.hbx_index_compact.argtypes = [P, P, ctypes.POINTER(IxCompactSummary)]
+    host = [U32, P, P, P]  # n_files, images, sizes, caps
+    L.hbx_index_lookup_host.argtypes = host + L.hbx_index_lookup.argtypes[2:]
+    L.hbx_index_scan_host.argtypes = host + L.hbx_index_scan.argtypes[2:]
+    L.hbx_index_mark_host.argtypes = host + L.hbx_index_mark.argtypes[2:]
+    L.hbx_index_update_host.argtypes = host + L.hbx_index_update.argtypes[2:]
+    L.hbx_index_sweep_host.argtypes = host + L.hbx_index_sweep.argtypes[2:]
+    L.hbx_index_compact_host.argtypes = host + L.hbx_index_compact.argtypes[2:]
     for name in EXPORTS:
         if name not in _NON_STATUS:
             getattr(L, name).restype = I

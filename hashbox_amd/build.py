@@ -15,6 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhbxgpu.so")
 SOURCES = ["hbx_engine.hip", "hbx_kernels.hip", "hbx_device.h", "hbx_formats.h", "hbx_deflate.hip", "hbx_inflate.hip", "hbx_inflate_split.hip", "hbx_dedup.hip", "hbx_match.hip", "hbx_locate.hip", "hbx_restore.hip", "hbx_restore_many.hip", "hbx_wire.h",
            "hbx_datfile.hip", "hbx_datfile.h", "hbx_graph.hip", "hbx_compact.hip", "hbx_compact.h",
+           "hbx_index.hip", "hbx_index.h", "hbx_index_calls.hip",
            os.path.join("..", "..", "include", "hbxgpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

@@ -49,10 +49,12 @@
 #include "hbx_datfile.hip"
 #include "hbx_graph.hip"
 #include "hbx_compact.hip"
+#include "hbx_index.hip"
 #include "hbx_formats.h"
 #include "hbx_wire.h"
 #include "hbx_datfile.h"
 #include "hbx_compact.h"
+#include "hbx_index.h"
 
 namespace {
 
@@ -181,6 +183,27 @@ struct hbx_idset {
   }
   void release() {
     for (DevBuf* d : {&d_keys, &d_slots, &d_ctl, &d_in, &d_flag, &d_scratch}) d->release();
+  }
+};
+
+// A store's index files in device memory (hbx_index_open; layout and kernels:
+// hbx_index.hip).  Every image has the capacity 16 + 24 * columns and is zero
+// behind its size.  Every kernel that touches it runs on the result stream.
+struct hbx_index {
+  uint32_t n = 0;
+  uint64_t columns = 0, tiles = 0;
+  uint64_t size[HBX_IX_FILES_MAX] = {};
+  hbxx::Tab tab;  // what d_tab holds
+  DevBuf img[HBX_IX_FILES_MAX], save[HBX_IX_FILES_MAX];
+  // the table, the counters, the tiles' scan, the live table; a call's IDs / records, hits and flags;
+  // the sweep's links, actions, targets, the deleted entries' ranks and records
+  DevBuf d_tab, d_stat, d_tiles, d_live, d_in, d_hits, d_out, d_link, d_act, d_moved, d_kflag, d_killed;
+  void release() {
+    for (DevBuf& d : img) d.release();
+    for (DevBuf& d : save) d.release();
+    for (DevBuf* d : {&d_tab, &d_stat, &d_tiles, &d_live, &d_in, &d_hits, &d_out, &d_link, &d_act, &d_moved, &d_kflag,
+                      &d_killed})
+      d->release();
   }
 };
 
@@ -451,6 +474,7 @@ struct hbx_ctx {
   // numbered at submit (dd_submitted) and must be enqueued in that order
   // (dd_marked, finalize_batch)
   std::vector<hbx_idset*> idsets;
+  std::vector<hbx_index*> indexes;  // hbx_index_open: the context's index handles
   DevBuf d_dscratch;
   uint64_t dd_submitted = 0, dd_marked = 0;
   uint64_t match_push_bytes = 0;  // hbx_knobs: bytes of the result pushes of match batches
@@ -1986,6 +2010,10 @@ void hbx_ctx_destroy(hbx_ctx* c) {
   for (hbx_idset* t : c->idsets) {
     t->release();
     delete t;
+  }
+  for (hbx_index* x : c->indexes) {
+    x->release();
+    delete x;
   }
   c->d_dscratch.release();
   for (DevBuf& d : c->d_mt) d.release();
@@ -6697,3 +6725,6 @@ int hbx_datfile_verify_at(hbx_ctx* c, const void* d_image, uint64_t size, const 
 }
 
 }  // extern "C"
+
+// ---- K17: the index files (DESIGN.md §5 "K17") -----------------------------
+#include "hbx_index_calls.hip"

@@ -423,6 +423,190 @@ class IdSet:
         self.close()
 
 
+IX_HIT_DTYPE = np.dtype([("found", np.uint32), ("flags", np.uint32), ("file", np.uint32), ("meta_file", np.uint32),
+                         ("offset", np.uint64), ("meta_off", np.uint64)])  # hbx_ix_hit
+IX_LIVE_DTYPE = np.dtype([("id", np.uint8, (16,)), ("flags", np.uint32), ("ix_file", np.uint32),
+                          ("ix_offset", np.uint64), ("meta_file", np.uint32), ("state", np.uint32),
+                          ("meta_off", np.uint64)])  # hbx_ix_live
+IX_KILLED_DTYPE = np.dtype([("id", np.uint8, (16,)), ("meta_file", np.uint32), ("reserved", np.uint32),
+                            ("meta_off", np.uint64)])  # hbx_ix_killed
+assert IX_HIT_DTYPE.itemsize == 32 and IX_LIVE_DTYPE.itemsize == 48 and IX_KILLED_DTYPE.itemsize == 32
+
+
+def _fields(s) -> dict:
+    return {k: int(getattr(s, k)) for k, _ in s._fields_}
+
+
+@dataclass(slots=True)
+class IndexScan:
+    """What :meth:`Index.scan` returns (hbx_index_scan): the pass of
+    CheckIndexes (pkg/storagedb/integrity.go:354-410) with CompactIndexes'
+    counters."""
+    live: np.ndarray  # IX_LIVE_DTYPE [n_live]: the live entries in (file, offset) order
+    per_file: list  # hbx_ix_file_stats' fields, one dict per file; first_misplaced is None without one
+    summary: dict  # hbx_ix_summary's fields
+
+
+@dataclass(slots=True)
+class IndexSweep:
+    """What :meth:`Index.sweep` returns (hbx_index_sweep): what SweepIndexes
+    (pkg/storagedb/gc.go:70-151) did, per live entry of the scan before it."""
+    action: np.ndarray  # uint8 [n_live]: IX_ACT_* (1 deleted, 2 stays, 3 obsolete, 4 moved, 5 abort)
+    moved_to: np.ndarray  # uint64 [n_live, 2]: (file, offset) of a moved entry, else 2^64 - 1 twice
+    killed: np.ndarray  # IX_KILLED_DTYPE [n_deleted]: killMetaEntry's arguments, in live order
+    summary: dict  # hbx_ix_sweep_summary's fields; first_abort is None without one
+
+
+class IndexSweepError(HbxError):
+    """:meth:`Index.sweep`: findIXOffset named a later place for an entry, where
+    the reference aborts (gc.go:129-131; HBX_ERR_FORMAT).  ``sweep`` is the
+    complete :class:`IndexSweep`; the index is unchanged."""
+
+    def __init__(self, msg: str, sweep: "IndexSweep"):
+        super().__init__(msg)
+        self.sweep = sweep
+
+
+class Index:
+    """A store's index files (``*.idx``) in device memory (hbx_index, K17): the
+    open-addressed tables of pkg/storagedb/index.go with the reference's
+    operations on them.  Nothing is written to disk: :meth:`export` hands the
+    images back."""
+
+    def __init__(self, engine: "Engine", source):
+        self._engine = engine
+        self._h = ctypes.c_void_p()
+        e = engine
+        src = list(source)
+        self.n_files = len(src)
+        if src and all(isinstance(s, (str, os.PathLike)) for s in src):
+            paths = (ctypes.c_char_p * len(src))(*[os.fsencode(s) for s in src])
+            rc = e._L.hbx_index_open_paths(e._ctx, len(src), paths, ctypes.byref(self._h))
+        else:
+            arrs = [np.ascontiguousarray(np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray, memoryview))
+                                         else np.asarray(s, np.uint8).reshape(-1)) for s in src]
+            ptrs = (ctypes.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+            sizes = np.array([a.shape[0] for a in arrs] + [0], np.uint64)
+            rc = e._L.hbx_index_open(e._ctx, len(arrs), ptrs, _p(sizes), ctypes.byref(self._h))
+        e._check(rc, "hbx_index_open")
+
+    def sizes(self) -> List[int]:
+        """Each file's current size (hbx_index_sizes)."""
+        e = self._engine
+        out = np.zeros(_lib.IX_FILES_MAX, np.uint64)
+        e._check(e._L.hbx_index_sizes(e._ctx, self._h, _p(out)), "hbx_index_sizes")
+        return out[:self.n_files].tolist()
+
+    def export(self, k: int) -> bytes:
+        """File ``k``'s image as it stands (hbx_index_export)."""
+        e = self._engine
+        out = np.zeros(max(self.sizes()[k], 1), np.uint8)
+        n = ctypes.c_uint64(0)
+        e._check(e._L.hbx_index_export(e._ctx, self._h, int(k), _p(out), out.shape[0], ctypes.byref(n)),
+                 "hbx_index_export")
+        return out[:int(n.value)].tobytes()
+
+    def lookup(self, ids, stop_on_free: bool = False) -> np.ndarray:
+        """findIXOffset (index.go:54-107) for every ID: IX_HIT_DTYPE [n].
+        ``file`` and ``offset`` are the rule's place whether found or not;
+        without ``stop_on_free`` this is readIXEntry."""
+        a = _ids_array(ids)
+        hits = np.zeros(max(a.shape[0], 1), IX_HIT_DTYPE)
+        e = self._engine
+        e._check(e._L.hbx_index_lookup(e._ctx, self._h, a.shape[0], _p(a), 1 if stop_on_free else 0, _p(hits)),
+                 "hbx_index_lookup")
+        return hits[:a.shape[0]]
+
+    def scan(self, live_cap: int = 0) -> IndexScan:
+        """One pass over every slot of every file (hbx_index_scan).  The live
+        table is sized from ``live_cap`` and, when the index holds more live
+        entries, from the library's count (the call then runs once more)."""
+        e = self._engine
+        per = (_lib.IxFileStats * _lib.IX_FILES_MAX)()
+        sm = _lib.IxSummary()
+        live = np.zeros(max(int(live_cap), 1), IX_LIVE_DTYPE)
+        for _ in range(2):
+            rc = e._L.hbx_index_scan(e._ctx, self._h, _p(live), live.shape[0], per, ctypes.byref(sm))
+            if rc != _lib.ERR_CAPACITY or int(sm.n_live) <= live.shape[0]:
+                break
+            live = np.zeros(int(sm.n_live), IX_LIVE_DTYPE)
+        e._check(rc, "hbx_index_scan")
+        files = [_fields(per[f]) for f in range(self.n_files)]
+        for f in files:
+            if f["first_misplaced"] == _lib.NO_DIFF:
+                f["first_misplaced"] = None
+        return IndexScan(live[:int(sm.n_live)], files, _fields(sm))
+
+    def mark(self, ids) -> np.ndarray:
+        """The write half of MarkIndexes (gc.go:46-54): Marked is set on the
+        slot of every ID readIXEntry finds (hbx_index_mark).  Returns bool [n],
+        False where the reference would abort (gc.go:36-37)."""
+        a = _ids_array(ids)
+        found = np.zeros(max(a.shape[0], 1), np.uint8)
+        e = self._engine
+        e._check(e._L.hbx_index_mark(e._ctx, self._h, a.shape[0], _p(a), _p(found), None), "hbx_index_mark")
+        return found[:a.shape[0]].astype(bool)
+
+    def update(self, recs) -> np.ndarray:
+        """changeMetaLocation (meta.go:122-128) from StorageIXEntry records,
+        uint8 [n, 24] as :attr:`DatCompact.ix` (hbx_index_update): the location
+        and the NoLinks bit of every ID readIXEntry finds.  Returns uint8 [n]:
+        0 updated, 1 not found (inserting is not done here)."""
+        r = np.ascontiguousarray(np.asarray(recs, np.uint8).reshape(-1, _lib.IX_ENTRY))
+        st = np.zeros(max(r.shape[0], 1), np.uint8)
+        e = self._engine
+        e._check(e._L.hbx_index_update(e._ctx, self._h, r.shape[0], _p(r) if r.shape[0] else None, _p(st)),
+                 "hbx_index_update")
+        return st[:r.shape[0]]
+
+    def sweep(self, live_cap: int = 0) -> IndexSweep:
+        """SweepIndexes (gc.go:70-151) with the Marked bits of the images
+        (hbx_index_sweep).  Raises :class:`IndexSweepError` where the reference
+        aborts; the index is then unchanged.  The outputs are sized from
+        ``live_cap`` and, when the index holds more live entries, from the
+        library's counts (a first call that changes nothing tells them)."""
+        e = self._engine
+        sm = _lib.IxSweepSummary()
+        n_live = n_del = int(live_cap)
+        for _ in range(2):
+            action = np.zeros(max(n_live, 1), np.uint8)
+            moved = np.zeros((max(n_live, 1), 2), np.uint64)
+            killed = np.zeros(max(n_del, 1), IX_KILLED_DTYPE)
+            rc = e._L.hbx_index_sweep(e._ctx, self._h, _p(action), _p(moved), n_live, _p(killed), n_del, ctypes.byref(sm))
+            if rc != _lib.ERR_CAPACITY or (int(sm.n_live) <= n_live and int(sm.swept_records) <= n_del):
+                break
+            n_live, n_del = int(sm.n_live), int(sm.swept_records)
+        summary = _fields(sm)
+        if summary["first_abort"] == _lib.NO_DIFF:
+            summary["first_abort"] = None
+        res = IndexSweep(action[:int(sm.n_live)], moved[:int(sm.n_live)], killed[:int(sm.n_deleted)], summary)
+        if rc == _lib.ERR_FORMAT:
+            msg = e._L.hbx_last_error(e._ctx)
+            raise IndexSweepError(f"hbx_index_sweep: HBX_ERR_FORMAT: {msg.decode() if msg else ''}", res)
+        e._check(rc, "hbx_index_sweep")
+        return res
+
+    def compact(self) -> dict:
+        """CompactIndexes (gc.go:153-206; hbx_index_compact): ``cleared`` and
+        the new ``sizes``."""
+        e = self._engine
+        sm = _lib.IxCompactSummary()
+        e._check(e._L.hbx_index_compact(e._ctx, self._h, ctypes.byref(sm)), "hbx_index_compact")
+        return {"cleared": int(sm.cleared), "sizes": [int(sm.size[f]) for f in range(self.n_files)]}
+
+    def close(self):
+        if self._h and self._engine._ctx:
+            e = self._engine
+            e._check(e._L.hbx_index_close(e._ctx, self._h), "hbx_index_close")
+        self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Engine:
     """One MI355X (one HIP stream) running the chunk + block-ID path."""
 
@@ -827,6 +1011,13 @@ class Engine:
             if arena is not None:
                 self._L.hbx_arena_free(self._ctx, arena)
         return st[:n]
+
+    def open_index(self, source) -> Index:
+        """A store's index files 0 .. n - 1 on the device (K17; hbx_index_open /
+        _open_paths): ``source`` is a sequence of paths, or of images (bytes or
+        uint8 arrays).  A size that is no header and whole slots, or a header
+        of another type or version, raises (HBX_ERR_FORMAT)."""
+        return Index(self, source)
 
     def compact_datfile(self, source, entries, keep, file_no: int = 0, dst_file_no: Optional[int] = None,
                         dst_base: int = 16, keep_prefix: bool = True, meta_file_no: int = 0, meta_base: int = 16,

@@ -371,6 +371,28 @@ def gc_keep(graph, file_no, force: bool = False) -> list:
     return [live[fno == f] for f in range(n_files)]
 
 
+def gc_sweep(ix, ids, g):
+    """A GC run over the index files ``ix`` (:meth:`Engine.open_index`):
+    MarkIndexes' writes for the rows the roots reach (``ids[g.marked]``: ``ids``
+    is the block table's ID array, ``g`` its :class:`BlockGraph`), then
+    SweepIndexes and CompactIndexes (pkg/storagedb/gc.go:24-206), all on the
+    device.  Returns the :class:`IndexSweep`; its ``killed`` are the caller's
+    killMetaEntry calls.  A marked ID the index does not hold raises, where the
+    reference aborts (gc.go:36-37).  Which entries of a data file to keep
+    (:meth:`Engine.compact_datfile`'s ``keep``) also needs the meta files and
+    is not derived here."""
+    a = np.asarray(ids, np.uint8).reshape(-1, 16)
+    marked = np.asarray(g.marked)
+    if a.shape[0] != marked.shape[0]:
+        raise ValueError("one ID per row of the graph")
+    found = ix.mark(a[marked])
+    if not found.all():
+        raise HbxError(f"{int((~found).sum())} marked blocks have no index entry")
+    res = ix.sweep()
+    ix.compact()
+    return res
+
+
 def _read_verified(eng: Engine, read_block, block_id: bytes, what: str) -> bytes:
     """ReadBlock + VerifyBlock of one directory or chain block: its data,
     inflated and hashed with its links on the device (Engine.restore_blocks)."""

@@ -1309,8 +1309,8 @@ int hbx_block_graph(hbx_ctx *ctx, uint64_t n, const uint8_t *ids, const uint32_t
  *  4. Index records.  One 24-byte StorageIXEntry per kept entry, in order, as
  *     a flat array: BE16 flags | id | sixByteLocation(meta_file_no, meta_off[i]);
  *     flags is HBX_IX_F_EXISTS, with HBX_IX_F_NOLINKS when n_links == 0
- *     (data.go:96-100).  Placing them in the open-addressed index files stays
- *     with the caller.
+ *     (data.go:96-100).  hbx_index_update puts them into index files held on
+ *     the device (entries that exist; inserting stays with the caller).
  *  5. Summary: the counts and bytes per class; deleted_bytes = size - 16 - the
  *     stayers' bytes - moved_bytes (the reference's `deleted` on a file without
  *     broken spans; 0 for size < 16).
@@ -1392,6 +1392,222 @@ int hbx_datfile_compact_path(hbx_ctx *ctx, const char *path, uint64_t n, const h
                              uint64_t *new_off, uint64_t *meta_off, uint8_t *moved_out, uint64_t moved_cap,
                              uint8_t *meta_out, uint64_t meta_cap, uint8_t *ix_out, uint64_t ix_cap,
                              hbx_dat_compact_summary *summary);
+
+/* ---- Index files on the device: probe, scan, mark, sweep, compact (K17) ------------
+ * The store finds a block through its *.idx files (pkg/storagedb/index.go):
+ * open-addressed tables of 24-byte StorageIXEntry records keyed by the last 24
+ * bits of the block ID.  A GC run is MarkIndexes -> SweepIndexes ->
+ * CompactIndexes (gc.go:24-206) and CheckIndexes reads every record
+ * (integrity.go:354-410); the reference does all of it on one goroutine with a
+ * seek and a read per probe.  An hbx_index holds the images of a store's index
+ * files 0 .. n_files - 1 in device memory and applies the reference's
+ * operations to them there (K17, hbx_index.hip), from hbx_index_open to
+ * hbx_index_export; nothing is written to disk.  hbx_index_*_host are the same
+ * operations over host images, in place, without a context or a device: what
+ * a device call leaves in its images and outputs equals what the _host call
+ * of the same name leaves, byte for byte and word for word.
+ *
+ * All integers are big-endian.
+ *   File.  A 16-byte header (BE32 "HSIX", BE32 version 1, 8 more bytes;
+ *     storagedb.go:40-49, as the data files'), then slots of 24 bytes: slot s
+ *     lies at offset 16 + 24 s.  A valid size has (size - 16) % 24 == 0 and
+ *     size <= HBX_IX_SIZE_MAX = 16 + 24 (2^24 + 682) (index.go:20-22).
+ *   Slot.  BE16 flags | id[16] | sixByteLocation (48 bits, file << 34 | offset:
+ *     where the block's meta entry lies; storagedb.go:90-106).
+ *   Flags.  HBX_IX_F_EXISTS 1, _NOLINKS 2, _MARKED 4, _INVALID 8
+ *     (storagedb.go:56-59).  A slot is LIVE if Exists is set and Invalid clear.
+ *   Home.  home(id) = id[13] << 16 | id[14] << 8 | id[15]; base(id) = 16 + 24 home
+ *     (calculateIXEntryOffset, index.go:48-50).
+ *
+ * THE RULE: findIXOffset(id, stop_on_free) (index.go:54-107).  Every call below
+ * is defined through it.
+ *   Start.  File f = 0, offset o = base(id).
+ *   Per file.  If there is no file f: stop.  If o > size[f]: stop.  Otherwise
+ *     make up to HBX_IX_PROBE_LIMIT (682) probes; each probe:
+ *       if o >= size[f]: stop (the reference's "room at the end").
+ *       Read the slot at o.
+ *       Live and all 16 ID bytes equal: FOUND (f, o).
+ *       Live with another ID: o += 24, next probe.
+ *       Anything else: remember (f, o) as the free place if none is remembered
+ *       yet; then stop if stop_on_free or the slot's Exists is clear, otherwise
+ *       o += 24, next probe.
+ *     After 682 probes: f++, o = base(id).
+ *   On stop.  Not found; the PLACE is the remembered free one, else the current
+ *     (f, o).  It may name a file that does not exist (f == n_files: "ran out
+ *     of index files") or an offset at or past a file's end.
+ * The semantics are those of that loop over a coherent image: the reference
+ * flushes its writer before every probe (ixFile.Size, bufferedfile.go:88-93),
+ * so a probe sees every earlier write.  readIXEntry(id) (index.go:109-115) is
+ * the rule with stop_on_free = 0.
+ *
+ * Conventions of the device calls, as hbx_datfile_* and hbx_block_graph:
+ * synchronous; HBX_ERR_STATE while batches are pending or after a failed
+ * submit; a handle of another context is HBX_ERR_ARG; an output capacity too
+ * small is HBX_ERR_CAPACITY with the needed counts in the summary and nothing
+ * changed; device memory is checked against the free memory before it is
+ * taken (HBX_ERR_CAPACITY); every stream is idle on return and the context
+ * stays usable after any failure; n == 0 is HBX_OK.  A handle keeps, beside
+ * its images, what its calls need (48 bytes per live entry for scan and sweep,
+ * 8 bytes per column and a second copy of the images during a sweep) until
+ * hbx_index_close; hbx_ctx_destroy closes what is still open. */
+#define HBX_IX_F_MARKED 4u        /* entryFlagMarked (storagedb.go:58) */
+#define HBX_IX_F_INVALID 8u       /* entryFlagInvalid */
+#define HBX_IX_HEADER 16u         /* storageFileHeaderSize */
+#define HBX_IX_PROBE_LIMIT 682u   /* storageIXEntryProbeLimit (index.go:21) */
+#define HBX_IX_FILETYPE 0x48534958u /* "HSIX" */
+#define HBX_IX_VERSION 1u
+#define HBX_IX_SLOTS_MAX ((1u << 24) + HBX_IX_PROBE_LIMIT)
+#define HBX_IX_SIZE_MAX (16ull + 24ull * HBX_IX_SLOTS_MAX) /* storageIXFileSize + the header */
+#define HBX_IX_FILES_MAX 16u      /* index files in one hbx_index */
+#define HBX_IX_SWEEP_TILE 256u    /* columns (slot numbers) per workgroup of the sweep kernel */
+#define HBX_IX_ACT_DELETED 1u
+#define HBX_IX_ACT_STAY 2u
+#define HBX_IX_ACT_OBSOLETE 3u
+#define HBX_IX_ACT_MOVED 4u
+#define HBX_IX_ACT_ABORT 5u
+typedef struct hbx_index hbx_index;
+typedef struct {
+  uint32_t found;     /* 1: the rule found the ID */
+  uint32_t flags;     /* the slot's flags (found), else 0 */
+  uint32_t file;      /* the rule's place, found or not; n_files = ran out of index files */
+  uint32_t meta_file; /* the slot's location (found), else 0 */
+  uint64_t offset;
+  uint64_t meta_off;
+} hbx_ix_hit;         /* 32 bytes */
+typedef struct {
+  uint8_t id[16];
+  uint32_t flags;
+  uint32_t ix_file;
+  uint64_t ix_offset;
+  uint32_t meta_file;
+  uint32_t state;     /* 0: readIXEntry(id) returns this slot; 1: another slot (this one is an obsolete
+                         duplicate); 2: none (the entry is cut off from its home) */
+  uint64_t meta_off;
+} hbx_ix_live;        /* 48 bytes */
+typedef struct {
+  uint64_t slots;
+  uint64_t n_live, n_invalid, n_empty; /* Invalid set: invalid, whatever else; neither: empty */
+  uint64_t n_marked, n_nolinks;        /* among the live ones */
+  uint64_t n_misplaced;                /* live with offset < base(id): CheckIndexes aborts (integrity.go:387-390) */
+  uint64_t first_misplaced;            /* the first such offset, UINT64_MAX without one */
+  uint64_t trunc_point;                /* 16 + 24 (the last live slot + 1); 16 without one */
+} hbx_ix_file_stats;                   /* 72 bytes */
+typedef struct {
+  uint64_t n_files, slots, n_live, n_invalid, n_empty, n_marked, n_nolinks, n_misplaced;
+  uint64_t n_obsolete, n_cut_off; /* live entries of state 1 and 2 */
+} hbx_ix_summary;                 /* 80 bytes */
+typedef struct {
+  uint8_t id[16];
+  uint32_t meta_file;
+  uint32_t reserved;
+  uint64_t meta_off;
+} hbx_ix_killed;      /* 32 bytes: killMetaEntry's arguments (gc.go:105-106) */
+typedef struct {
+  uint64_t n_live; /* live entries before the sweep: what action and moved_to must hold */
+  uint64_t n_deleted, n_stay, n_obsolete, n_moved, n_abort;
+  uint64_t first_abort;   /* the first live entry with HBX_IX_ACT_ABORT, UINT64_MAX without one */
+  uint64_t swept_records; /* = n_deleted: what killed must hold */
+  uint64_t n_grown;       /* files a move has lengthened */
+} hbx_ix_sweep_summary;   /* 72 bytes */
+typedef struct {
+  uint64_t n_files;
+  uint64_t cleared;                /* slots blanked */
+  uint64_t size[HBX_IX_FILES_MAX]; /* each file's new size */
+} hbx_ix_compact_summary;          /* 144 bytes */
+
+/* Open: the images (host memory) of index files 0 .. n_files - 1 copied to the
+ * device.  HBX_ERR_ARG: n_files == 0 or above HBX_IX_FILES_MAX, a NULL.
+ * HBX_ERR_FORMAT: a size that is not valid (CheckIndexes aborts on it,
+ * integrity.go:365-367), a header with another type or version (as
+ * CheckStorageFiles, storagedb.go:150-165).  _paths reads each file through
+ * the reader of hbx_datfile_check_path (HBX_ERR_IO). */
+int hbx_index_open(hbx_ctx *ctx, uint32_t n_files, const uint8_t *const *images, const uint64_t *sizes,
+                   hbx_index **out);
+int hbx_index_open_paths(hbx_ctx *ctx, uint32_t n_files, const char *const *paths, hbx_index **out);
+int hbx_index_close(hbx_ctx *ctx, hbx_index *ix);
+/* sizes[n_files]: each file's current size (a sweep may lengthen, a compaction shorten it). */
+int hbx_index_sizes(hbx_ctx *ctx, hbx_index *ix, uint64_t *sizes);
+/* File `file`'s image as it stands into out (cap bytes), *n its size. */
+int hbx_index_export(hbx_ctx *ctx, hbx_index *ix, uint32_t file, uint8_t *out, uint64_t cap, uint64_t *n);
+/* The rule for n IDs (16 bytes each): hits[i].  With stop_on_free == 0 this is
+ * readIXEntry.  The probe kernel: one lane per ID, a slot read as three 64-bit
+ * words, the ID compared as two. */
+int hbx_index_lookup(hbx_ctx *ctx, hbx_index *ix, uint64_t n, const uint8_t *ids, int stop_on_free,
+                     hbx_ix_hit *hits);
+/* One pass over every slot of every file: the pass of CheckIndexes, with
+ * CompactIndexes' counters.  per_file[n_files] (may be NULL), *summary, and
+ * live[j], the live entries in (file, offset) order (live may be NULL with
+ * live_cap 0: only counted).  HBX_ERR_CAPACITY if live_cap < n_live: the
+ * statistics are complete and live holds the first live_cap entries. */
+int hbx_index_scan(hbx_ctx *ctx, hbx_index *ix, hbx_ix_live *live, uint64_t live_cap,
+                   hbx_ix_file_stats *per_file, hbx_ix_summary *summary);
+/* The write half of MarkIndexes (gc.go:46-54): for every ID readIXEntry finds,
+ * Marked is set in that slot and nothing else changes (idempotent: an ID may
+ * repeat).  found[i] (may be NULL) is 0 where the reference aborts
+ * (gc.go:36-37); *n_missing (may be NULL) counts those.  The graph walk is
+ * hbx_block_graph's: its mark selects the IDs. */
+int hbx_index_mark(hbx_ctx *ctx, hbx_index *ix, uint64_t n, const uint8_t *ids, uint8_t *found,
+                   uint64_t *n_missing);
+/* changeMetaLocation (meta.go:122-128) and RecoverData's repair of an existing
+ * entry (integrity.go:216-240) from n StorageIXEntry records (24 bytes each,
+ * as hbx_datfile_compact_* returns them): where readIXEntry finds a record's ID, the
+ * slot's location becomes the record's and its NoLinks bit the record's, every
+ * other bit stays, status[i] = 0; where it does not, status[i] = 1 and nothing
+ * is written.  INSERTING a new ID is not done here.  An ID that occurs twice in
+ * one call is HBX_ERR_ARG, checked on the host before anything is launched. */
+int hbx_index_update(hbx_ctx *ctx, hbx_index *ix, uint64_t n, const uint8_t *recs, uint8_t *status);
+/* SweepIndexes (gc.go:70-151), the Marked bits read from the images.  The files
+ * are walked in order, each from its first slot to the end it had when the
+ * sweep began; an Invalid slot is skipped whatever else it holds, a slot with
+ * Exists clear is not touched.  Live entry j (hbx_index_scan's order, before
+ * the sweep) gets action[j]:
+ *   HBX_IX_ACT_DELETED   Marked was clear: Invalid is set, the other bits stay;
+ *     (id, meta_file, meta_off) is appended to killed, in live order.
+ *   Otherwise Marked is cleared and the rule runs with stop_on_free = 1 over
+ *   the images as they stand at that moment:
+ *   HBX_IX_ACT_STAY      the place is this slot.
+ *   HBX_IX_ACT_OBSOLETE  found elsewhere: Invalid is set.
+ *   HBX_IX_ACT_MOVED     not found and the place lies in an earlier file, or
+ *     earlier in this one (gc.go:121-128): the entry is written there without
+ *     Marked, moved_to[2j] = its file, moved_to[2j + 1] = its offset, and the
+ *     old slot gets Invalid.  A place past an earlier file's end lengthens that
+ *     file to the end of the written slot; the bytes between are zero.
+ *   HBX_IX_ACT_ABORT     any other place (gc.go:129-131, where the reference
+ *     aborts): the entry is left as it is, Marked too, and the sweep goes on.
+ * moved_to is UINT64_MAX twice for every other action.  If any entry got
+ * HBX_IX_ACT_ABORT the call returns HBX_ERR_FORMAT: action, moved_to, killed
+ * and the summary are as described and THE INDEX IS UNCHANGED.
+ * HBX_ERR_CAPACITY: live_cap < n_live or killed_cap < n_deleted; the summary
+ * holds n_live and n_deleted = swept_records, nothing else, and the index is
+ * unchanged.  The _host form also returns it, index unchanged, when a file
+ * would grow past its caps[f].
+ * On the device the order-dependent loop runs in parallel over ranges of
+ * columns (slot numbers shared by all files) no entry's reads and writes
+ * cross: hbx_index.hip says how they are cut. */
+int hbx_index_sweep(hbx_ctx *ctx, hbx_index *ix, uint8_t *action, uint64_t *moved_to, uint64_t live_cap,
+                    hbx_ix_killed *killed, uint64_t killed_cap, hbx_ix_sweep_summary *summary);
+/* CompactIndexes (gc.go:153-206): every slot with Invalid set becomes 24 zero
+ * bytes; each file's size becomes 16 + 24 (its last live slot + 1), 16 without
+ * one. */
+int hbx_index_compact(hbx_ctx *ctx, hbx_index *ix, hbx_ix_compact_summary *summary);
+/* The same operations over host images, in place (no context, no device; the
+ * checks of hbx_index_open on every call).  sizes[f] is read, and written by
+ * sweep and compact; caps[f] is what images[f] can hold (only the sweep reads
+ * it; NULL elsewhere). */
+int hbx_index_lookup_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                          uint64_t n, const uint8_t *ids, int stop_on_free, hbx_ix_hit *hits);
+int hbx_index_scan_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                        hbx_ix_live *live, uint64_t live_cap, hbx_ix_file_stats *per_file,
+                        hbx_ix_summary *summary);
+int hbx_index_mark_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                        uint64_t n, const uint8_t *ids, uint8_t *found, uint64_t *n_missing);
+int hbx_index_update_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                          uint64_t n, const uint8_t *recs, uint8_t *status);
+int hbx_index_sweep_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                         uint8_t *action, uint64_t *moved_to, uint64_t live_cap, hbx_ix_killed *killed,
+                         uint64_t killed_cap, hbx_ix_sweep_summary *summary);
+int hbx_index_compact_host(uint32_t n_files, uint8_t *const *images, uint64_t *sizes, const uint64_t *caps,
+                           hbx_ix_compact_summary *summary);
 
 /* Device arena helpers (allocations include HBX_ARENA_SLACK). */
 int hbx_arena_alloc(hbx_ctx *ctx, uint64_t bytes, void **d_ptr);
